@@ -5,8 +5,15 @@ A step = forward of the unrolled 8-step chain + backward + (N>1: one RCCL all-re
 of the flat gradient over xGMI) + clip/Adam, on one synthetic [B,64,64,3] batch per
 GPU (B=128, weak scaling).  Inputs are resident in HBM before the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config celeba]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config celeba] [--dump-outputs DIR] [--full]
 N>1 is launched by the driver via torch.distributed.run (one rank per GPU).
+
+A plain run does what `value` needs and nothing else: set-up, warm-up, the K timed steps (with the
+dominant kernel's event probe inside them, as always), the outputs if --dump-outputs is given, and the
+result line.  --full adds every other leg after the timed region: the secondary-kernel probe and its
+isolated launches, the other precision modes (bf16_value / parity_value, fp32_value), the fp32 step's
+dominant-kernel timing, and the CPU baseline; --no-secondary, --no-cpu-baseline, --no-fp32 and
+--no-fp32-mode trim it.
 """
 import argparse
 import ctypes
@@ -209,6 +216,28 @@ def pmc_traffic(kernel, key="celeba/bf16"):
     return None, None
 
 
+DUMP_BUDGET = 64 << 20  # bytes of --dump-outputs, all files together
+
+
+def dump_outputs(dirname, arrays, seed=0):
+    """--dump-outputs: write each array of `arrays` (name -> ndarray) as <dirname>/<name>.npy, float64 where it
+    is float64 and float32 otherwise, DUMP_BUDGET bytes at the most in all.  Arrays are taken smallest first and
+    each may use an equal share of what is left, so small ones are whole; a larger one becomes a 1-D sample of
+    its flattened elements at fixed indices (sorted draws of default_rng(seed): the same for every run and
+    build of the same shapes)."""
+    os.makedirs(dirname, exist_ok=True)
+    left = DUMP_BUDGET - 1024 * len(arrays)  # the .npy headers
+    todo = sorted(arrays.items(), key=lambda kv: kv[1].size * kv[1].dtype.itemsize)
+    for i, (name, a) in enumerate(todo):
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        cap = left // (len(todo) - i) // a.dtype.itemsize
+        if a.size > cap:
+            idx = np.unique(np.random.default_rng(seed).integers(0, a.size, cap))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        left -= a.size * a.dtype.itemsize
+
+
 def _cpu_threads():
     """Host threads for the CPU baseline: the physical cores this process may use, capped by the
     box's CPU share (OMP_NUM_THREADS, set to 16 on the GPU boxes)."""
@@ -388,12 +417,17 @@ def run_pixelvae(args, cfgmod):
     FLOPs (and so step_achieved_tflops) are ESTIMATED as 3x the forward convolution FLOPs (forward +
     input gradient + weight gradient); only the forward launches are timed."""
     PV = importlib.import_module(PKG + ".pixelvae").PixelVAE
+    torch.manual_seed(1234)  # the sampler's uniforms and the dropout seeds come from torch's generators
     B = args.batch or 128
     dtype = args.dtype
     cap = args.probe_launches or 96
     value, ms, probe, elbo, head_flops, pv, x = _pv_throughput(PV, B, dtype, args.steps, args.warmup, cap)
     c = pv.cfg
     planes = pv.head.planes
+    if args.dump_outputs:  # the last timed step: its loss and reconstruction, the parameters it left
+        dump_outputs(args.dump_outputs, {
+            "loss": np.array([pv.loss_value()], np.float64), "xhat": pv.xhat(pv.e).cpu().numpy(),
+            "params": pv.vae.params.cpu().numpy(), "head_params": pv.head.P.cpu().numpy()})
     vae_flops = conv_flops_per_img(c) * B  # the engine's part (both steps' recognition + step 0 ladder)
     alt = "bf16" if dtype != "bf16" else "bf16x6"
     alt_value = alt_ms = alt_roof = None
@@ -419,6 +453,7 @@ def run_pixelvae(args, cfgmod):
         "config": {"workload": METRIC["c_pixelvae"][1], "model": "c_pixelvae", "global_batch": B, "per_gpu_batch": B,
                    "image": [c.height, c.width, c.channels], "mc_steps": c.mc_steps, "parallelism": "dp1"},
         "elbo_per_img": round(elbo, 5),
+        "full": args.full, "dump_outputs": args.dump_outputs,
         "parity": parity,
         "parity_value": round(value, 2) if parity else (None if alt_value is None else round(alt_value, 2)),
         "parity_ms_per_step": round(ms, 3) if parity else (None if alt_ms is None else round(alt_ms, 3)),
@@ -459,6 +494,14 @@ def make_parser():
     ap.add_argument("--warmup-seconds", type=float, default=1.0,
                     help="after the --warmup steps, more untimed steps until this much warm-up has run (0: off); "
                          "--steps and what is timed are unchanged")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run every other leg (secondary-kernel probe, other precision "
+                         "modes, the fp32 step's dominant-kernel timing, CPU baseline); a plain run has none of them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (loss, per-step statistics, "
+                         "per-image ELBO, the final reconstruction, the updated parameters) as DIR/<name>.npy, 64 MB "
+                         "at the most (a fixed sample of a larger array).  The step count must not depend on the "
+                         "clock, so the time-based warm-up is off: exactly --warmup steps run before the timed ones")
     ap.add_argument("--config", default="celeba")
     ap.add_argument("--batch", type=int, default=None)
     # bf16x6 (split-bf16 MFMA, held to the fp32 parity bounds in tests/test_headline_gpu.py) is the
@@ -500,6 +543,10 @@ def init_distributed(args, world, local):
 
 def main():
     args = make_parser().parse_args()
+    if not args.full:  # a plain run: the timed steps and nothing after them
+        args.no_secondary = args.no_cpu_baseline = True
+    if args.dump_outputs:  # the same steps on the same inputs in every run
+        args.warmup_seconds = 0.0
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(_spawn_ranks(args.gpus))
@@ -595,6 +642,11 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:  # the last timed step, before any later leg steps again
+        dump_outputs(args.dump_outputs, {
+            "loss": np.array([net.loss_value()], np.float64), "step_stats": net.step_stats().cpu().numpy(),
+            "elbo_per_image": net.elbo_per_image().cpu().numpy(), "xhat": net.xhat(-1).cpu().numpy(),
+            "params": net.params.cpu().numpy()})
     probe = None
     if probe_kid is not None and rank == 0:
         n, nt = ctypes.c_int64(), ctypes.c_int64()
@@ -659,7 +711,7 @@ def main():
         if nprod > 1:  # the MFMA work the plane products really run
             roof["issued"] = round(nprod * ach, 3)
             roof["frac_issued"] = round(nprod * ach / BF16_MFMA_PEAK_TFLOPS, 5)
-    elif rank == 0:
+    elif rank == 0 and args.full:
         shape = dominant_kernel_shape(cfg)
         sec, kflops = time_dominant_kernel(L, shape)
         ach = kflops / sec / 1e12
@@ -720,6 +772,8 @@ def main():
                        "parallelism": "dp%d" % world,
                        "grad_allreduce": ("per-step buckets overlapped with the backward" if overlap else "one call after the backward") if world > 1 else None},
             "elbo_per_img": round(elbo, 5),
+            "full": args.full,
+            "dump_outputs": args.dump_outputs,
             # bf16x6 and fp32 are held to the fp32 parity bounds (tests/test_headline_gpu.py); plain bf16
             # operands are not (x_hat_7 / gradients decorrelate from float64 at T=8): bf16 is labelled
             "parity": args.dtype != "bf16",

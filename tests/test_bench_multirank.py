@@ -35,6 +35,37 @@ def test_default_process_group_is_rccl():
     assert b.init_distributed(args, 1, 0) is None  # N = 1: no process group
 
 
+def test_plain_run_has_no_extra_legs():
+    b = _bench()
+    args = b.make_parser().parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert args.full is False and args.dump_outputs is None and args.steps == 3
+    args = b.make_parser().parse_args(["--full", "--dump-outputs", "d"])
+    assert args.full is True and args.dump_outputs == "d"
+
+
+def test_dump_outputs_budget(tmp_path, monkeypatch):
+    """--dump-outputs: small arrays whole (float64 kept, the rest float32), a large one a sample at the same
+    indices in every call, all files together within the budget."""
+    import numpy as np
+    b = _bench()
+    monkeypatch.setattr(b, "DUMP_BUDGET", 64 << 10)
+    rng = np.random.default_rng(0)
+    arrays = {"loss": np.array([1.5], np.float64), "stats": rng.standard_normal((8, 2)).astype(np.float32),
+              "big": rng.standard_normal((50, 40, 30)).astype(np.float32), "half": np.arange(7, dtype=np.float16)}
+    d1, d2 = str(tmp_path / "a"), str(tmp_path / "b")
+    b.dump_outputs(d1, arrays)
+    b.dump_outputs(d2, {k: v + 0 for k, v in arrays.items()})
+    assert sorted(os.listdir(d1)) == ["big.npy", "half.npy", "loss.npy", "stats.npy"]
+    assert sum(os.path.getsize(os.path.join(d1, f)) for f in os.listdir(d1)) <= 64 << 10
+    got = {k: np.load(os.path.join(d1, k + ".npy")) for k in arrays}
+    assert got["loss"].dtype == np.float64 and got["half"].dtype == np.float32 and got["big"].dtype == np.float32
+    assert np.array_equal(got["loss"], arrays["loss"]) and np.array_equal(got["stats"], arrays["stats"])
+    assert got["big"].ndim == 1 and 10000 < got["big"].size < arrays["big"].size
+    assert np.isin(got["big"], arrays["big"]).all()
+    for k in arrays:
+        assert np.array_equal(got[k], np.load(os.path.join(d2, k + ".npy")))
+
+
 @pytest.mark.gpu
 def test_bench_two_ranks_one_gpu(tmp_path):
     env = dict(os.environ)
