@@ -87,6 +87,18 @@ typedef struct svae_config {
    * recognition (z_t, KL_t) and creates no encoder / generator variables for them.  The caller hands
    * d loss / d x_hat_{e-1} and d loss / d z_t back with svae_set_external_grads.  0 = off. */
   int32_t external_generator_from;
+  /* Flat generator (the "infusion" netnames c_infusion_test :769, c_homog_infusion_test :775 / :793,
+   * m_infusion_test :781; generator_flat :1880-1936): step 0 stays the ladder generator; every step
+   * t >= 1 maps the previous sample to x_hat_t through flat_conv_layers - 1 conv2d_bn_lrelu (4x4,
+   * stride 1, flat_conv_filter_sizes[1..] channels) and one sigmoid conv2d (xavier, live bias) at full
+   * resolution, in scope theta/generative_flat_step_<t> (share_theta: theta/generative_network_flat).
+   * No encoder, split-latent, highway or shortcut: z_t (t >= 1) reaches the loss through its KL term
+   * only.  Requires add_noise_to_chain; not with predict_generator_noise, predict_latent_code,
+   * add_improvement_maximization_loss or external_generator_from.  flat_conv_layers in [1, 8]; the
+   * sizes in [1, 32], [0] = channels; entry flat_conv_layers is never read (:245-247). */
+  int32_t flat_generator;
+  int32_t flat_conv_layers;
+  int32_t flat_conv_filter_sizes[9];
 } svae_config;
 
 typedef struct svae_param_desc {
@@ -230,6 +242,21 @@ int svae_op_conv_dgrad(const float* dy, int n, int h, int cin, const float* w, i
                        float* dx, void* stream);
 int svae_op_conv_wgrad(const float* x, int n, int h, int cin, const float* dy, int cout, int stride, int transpose,
                        float* dw, void* scratch, int64_t scratch_bytes, void* stream);
+/* Flat-generator layer (4x4 stride-1 TF-SAME conv, W [4,4,cin,cout], cin, cout <= 32; exact fp32 on
+ * v_mfma_f32_16x16x4_f32).  in_mean / in_invstd / in_beta != NULL: the conv reads lrelu(bn(x)) of
+ * the producer's pre-BN tensor x (zeros pad the activated tensor); NULL: x as it is.  stats_out
+ * (optional): 2*cout floats, (sum, sum of squares) of y per channel, interleaved.  SVAE_EBADCONFIG
+ * when the block's window does not fit the LDS.  With stats_out the call keeps a process-wide device
+ * scratch for the block partials, grown (device synchronise + reallocation) when a larger shape comes
+ * and never freed: a test entry point, not for stream capture or concurrent callers (the engine's own
+ * partials live in its arena). */
+int svae_op_flat_conv(const float* x, int n, int h, int cin, const float* w, int cout, const float* in_mean,
+                      const float* in_invstd, const float* in_beta, float* y, float* stats_out, void* stream);
+/* its input gradient dx [n,h,h,cin] from dy [n,h,h,cout], and its weight gradient dw [4,4,cin,cout]
+ * (scratch: the per-block slabs, >= ceil(h / max(1, 256 / h)) * n * 16*cin*cout floats) */
+int svae_op_flat_dgrad(const float* dy, int n, int h, int cin, const float* w, int cout, float* dx, void* stream);
+int svae_op_flat_wgrad(const float* x, int n, int h, int cin, const float* dy, int cout, float* dw, void* scratch,
+                       int64_t scratch_bytes, void* stream);
 /* training BN (+act 0 none,1 relu,2 lrelu) over rows of x [rows,C].
  * scratch: >= 1032*c bytes (sharded fixed-point column accumulators + constants); bwd: >= 1024*c bytes */
 int svae_op_bn_act(const float* x, int64_t rows, int c, const float* beta, int act, float* y, float* mean,

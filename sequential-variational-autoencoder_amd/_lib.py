@@ -37,6 +37,8 @@ class SvaeConfig(ctypes.Structure):
         ("predict_generator_stddev_max", ctypes.c_float), ("stddev_layers", ctypes.c_int32),
         ("stddev_filter_sizes", ctypes.c_int32 * 8), ("add_improvement_maximization_loss", ctypes.c_int32),
         ("latent_pred_loss_coeff", ctypes.c_float), ("external_generator_from", ctypes.c_int32),
+        ("flat_generator", ctypes.c_int32), ("flat_conv_layers", ctypes.c_int32),
+        ("flat_conv_filter_sizes", ctypes.c_int32 * 9),
     ]
 
 
@@ -123,6 +125,9 @@ def _load(path):
         "svae_op_bn_act": ([vp, i64, i32, vp, i32, vp, vp, vp, vp, i64, vp], i32),
         "svae_op_bn_act_bwd": ([vp, vp, vp, i64, i32, vp, vp, i32, vp, vp, vp, i64, vp], i32),
         "svae_op_fc": ([vp, i32, i32, vp, i32, vp, vp], i32),
+        "svae_op_flat_conv": ([vp, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp], i32),
+        "svae_op_flat_dgrad": ([vp, i32, i32, i32, vp, i32, vp, vp], i32),
+        "svae_op_flat_wgrad": ([vp, i32, i32, i32, vp, i32, vp, vp, i64, vp], i32),
         "svae_op_gather_bf16": ([vp, i32, i32, i32, vp, i32, i32, i32, i32, vp, vp, i64, vp], i32),
         "svae_op_wgrad_bf16": ([vp, i32, i32, i32, vp, i32, i32, i32, i32, vp, vp, i64, vp], i32),
         "svae_probe_begin": ([vp, i32, i32], i32),
@@ -198,7 +203,8 @@ EXPORTED = ["svae_param_count", "svae_param_layout", "svae_create", "svae_destro
             "svae_op_gather_bf16", "svae_op_wgrad_bf16", "svae_generate", "svae_set_backward_hook",
             "svae_hook_stream", "svae_adam_range", "svae_backward_adam", "svae_adam_state",
             "svae_set_chain_noise", "svae_bind_imp", "svae_backward_imp", "svae_adam_imp", "svae_imp_range",
-            "svae_set_external_grads", "svae_build_hash"]
+            "svae_set_external_grads", "svae_build_hash", "svae_op_flat_conv", "svae_op_flat_dgrad",
+            "svae_op_flat_wgrad"]
 # include/svae_pcnn.h (the PixelCNN++ head)
 PCNN_EXPORTED = ["svae_pcnn_wnorm", "svae_pcnn_wnorm_bwd", "svae_pcnn_conv", "svae_pcnn_conv_wgrad", "svae_pcnn_colsum",
                  "svae_pcnn_colsum_absmax", "svae_pcnn_im2col_h16", "svae_pcnn_conv_planes_amax",

@@ -54,6 +54,21 @@ class SVAEConfig:
     # c_pixelvae (generator = generator_pixelcnn, :535): steps t >= this run the PixelCNN++ head
     # (pixelvae.PixelVAE); the engine runs their recognition only.  0 = off
     external_generator_from: int = 0
+    # flat generator (generator_flat :1880-1936, the "infusion" netnames :769-793): steps t >= 1 are
+    # flat_conv_layers 4x4 stride-1 convolutions on the previous sample at full resolution
+    flat_generator: bool = False
+    flat_conv_layers: int = 6                         # :245
+    flat_conv_filter_sizes: Tuple[int, ...] = None    # :246-247 (None = [C, 2C, 4C, 8C, 4C, 2C, C])
+
+    def flat_sizes(self):
+        """flat_conv_filter_sizes (sequential_vae.py:246-247); entry flat_conv_layers is never read (:1926)."""
+        fs = self.flat_conv_filter_sizes
+        if fs is None:
+            c = self.channels
+            fs = [c, 2 * c, 4 * c, 8 * c, 4 * c, 2 * c, c]
+        if len(fs) < self.flat_conv_layers:
+            raise ValueError("flat_conv_filter_sizes needs flat_conv_layers = %d entries" % self.flat_conv_layers)
+        return [int(v) for v in fs]
 
     def noise_list(self):
         """noise_stddevs[t] per step (sequential_vae.py:239; the reference indexes noise_stddevs[step])."""
@@ -111,6 +126,11 @@ class SVAEConfig:
         c.add_improvement_maximization_loss = int(self.add_improvement_maximization_loss)
         c.latent_pred_loss_coeff = self.latent_pred_loss_coeff
         c.external_generator_from = int(self.external_generator_from)
+        c.flat_generator = int(self.flat_generator)
+        c.flat_conv_layers = int(self.flat_conv_layers)
+        if self.flat_generator:
+            for i, f in enumerate(self.flat_sizes()[:9]):
+                c.flat_conv_filter_sizes[i] = f
         return c
 
     def as_dict(self):
@@ -135,7 +155,9 @@ class SVAEConfig:
                     stddev_filter_sizes=tuple(self.predict_generator_stddev_filter_sizes),
                     add_improvement_maximization_loss=self.add_improvement_maximization_loss,
                     latent_pred_loss_coeff=self.latent_pred_loss_coeff,
-                    external_generator_from=self.external_generator_from)
+                    external_generator_from=self.external_generator_from,
+                    flat_generator=self.flat_generator, flat_conv_layers=self.flat_conv_layers,
+                    flat_conv_filter_sizes=(tuple(self.flat_sizes()) if self.flat_generator else None))
 
     def kl_on(self, t):
         """1 if step t's KL term enters self.loss (sequential_vae.py:1154, :1170-1172), else 0."""
@@ -191,6 +213,19 @@ PRESETS = {
                              filter_sizes=[3, 16, 32, 64, 128, 384], share_theta_weights=True,
                              share_phi_weights=True, regularized_steps=(0,), first_step_loss_coeff=2.0,
                              external_generator_from=1),
+    # "infusion" ablation (:769-793): step 0 a VLAE, every later step generator_flat on the previous sample
+    "c_infusion_test": SVAEConfig(add_noise_to_chain=True, flat_generator=True),                    # :769-773
+    "c_homog_infusion_test": SVAEConfig(add_noise_to_chain=True, flat_generator=True,
+                                        share_theta_weights=True, share_phi_weights=True),          # :775-779, :793
+    "m_infusion_test": SVAEConfig(batch=64, height=32, width=32, channels=1, levels=3,
+                                  filter_sizes=[1, 64, 128, 192, 256], latent_dims=[2, 2, 2], mc_steps=5,
+                                  range=(0.0, 1.0), add_noise_to_chain=True, flat_generator=True),  # :781-791
+    "tiny_flat": SVAEConfig(batch=4, height=32, width=32, channels=3, levels=4, filter_sizes=[3, 8, 8, 16, 24, 16],
+                            latent_dims=[2, 2, 3, 2], mc_steps=3, add_noise_to_chain=True, flat_generator=True),
+    "tiny_flat_homog": SVAEConfig(batch=4, height=32, width=32, channels=3, levels=4,
+                                  filter_sizes=[3, 8, 8, 16, 24, 16], latent_dims=[2, 2, 3, 2], mc_steps=3,
+                                  add_noise_to_chain=True, flat_generator=True, share_theta_weights=True,
+                                  share_phi_weights=True),
     "tiny_homog": SVAEConfig(batch=4, height=32, width=32, channels=3, levels=4, filter_sizes=[3, 8, 8, 16, 24, 16],
                              latent_dims=[2, 2, 3, 2], mc_steps=3, share_theta_weights=True,
                              share_phi_weights=True),

@@ -73,6 +73,13 @@ struct GenStep {
   long long owsd = 0, obsd = 0;
 };
 
+// generator_flat of one step (:1880-1936): nl - 1 conv2d_bn_lrelu + the sigmoid output conv
+struct FlatStep {
+  ConvL l[8];
+  int wout = -1, bout = -1;
+  long long owout = 0, obout = 0;
+};
+
 struct Geo {
   int B, H, W, C, L, T;
   int F[10], D[8], S[10];
@@ -98,6 +105,11 @@ struct Geo {
   float nstd[64];             // noise_stddevs
   float sd_max, lp_coef;      // predict_generator_stddev_max, latent_pred_loss_coeff
   int sd_nl, sd_F[9];         // stddev network: layers and channels (sd_F[0] = C)
+  // flat generator (generator_flat :1880-1936): steps t >= 1 are fl_nl 4x4 stride-1 convs on the
+  // previous sample, channels fl_F[0] = C .. fl_F[fl_nl] = C.  Te = 1 then: the ladder generator, its
+  // encoder and split-latent exist for step 0 only, exactly as for an external generator
+  bool flat;
+  int fl_nl, fl_F[9];
   // weight of step t's KL term relative to reg * c_first (compute_and_accumulate_loss :1154-1172)
   float kl_on(int t) const {
     if ((unreg >> t) & 1ULL) return 0.f;
@@ -145,6 +157,10 @@ bool make_geo(const svae_config* c, Geo& g, std::string& err) {
   g.share_theta = c->share_theta != 0;
   g.share_phi = c->share_phi != 0;
   g.Te = g.T;
+  if (c->flat_generator && c->external_generator_from != 0) {
+    err = "flat_generator: external_generator_from is not supported with it";
+    return false;
+  }
   if (c->external_generator_from != 0) {
     if (c->external_generator_from < 1 || c->external_generator_from >= g.T) {
       err = "external_generator_from must be in [1, mc_steps)";
@@ -179,6 +195,30 @@ bool make_geo(const svae_config* c, Geo& g, std::string& err) {
     }
     if (!(g.sd_max > 0.f)) { err = "predict_generator_stddev_max must be > 0"; return false; }
     if (g.H % 4) { err = "predict_generator_noise needs an image size divisible by 4"; return false; }
+  }
+  g.flat = c->flat_generator != 0;
+  g.fl_nl = 0;
+  if (g.flat) {
+    // generator_flat returns noise_stddevs[step] whatever add_noise_to_chain says (:1936); that quirk is
+    // not reproduced: every netname that selects it sets add_noise_to_chain
+    if (!g.noisy) { err = "flat_generator requires add_noise_to_chain"; return false; }
+    if (g.pgn) { err = "flat_generator: predict_generator_noise is not implemented for it (:1905)"; return false; }
+    if (g.plc) { err = "flat_generator: predict_latent_code is not supported with it"; return false; }
+    if (g.imp) { err = "flat_generator: add_improvement_maximization_loss is not supported with it"; return false; }
+    g.fl_nl = c->flat_conv_layers;
+    if (g.fl_nl < 1 || g.fl_nl > 8) { err = "flat_conv_layers must be in [1,8]"; return false; }
+    for (int i = 0; i < g.fl_nl; ++i) {
+      g.fl_F[i] = c->flat_conv_filter_sizes[i];
+      if (g.fl_F[i] < 1 || g.fl_F[i] > 32) { err = "flat_conv_filter_sizes must be in [1,32]"; return false; }
+    }
+    if (g.fl_F[0] != g.C) { err = "flat_conv_filter_sizes[0] must equal channels"; return false; }
+    g.fl_F[g.fl_nl] = g.C;  // the output conv (the list's own last entry is never read, :1926)
+    for (int i = 0; i < g.fl_nl; ++i)
+      if (!flat_conv_ok(g.B, g.H, g.fl_F[i], g.fl_F[i + 1]) || !flat_wgrad_ok(g.B, g.H, g.fl_F[i], g.fl_F[i + 1])) {
+        err = "flat_generator: the image rows of a block do not fit the LDS window at this size";
+        return false;
+      }
+    g.Te = std::min(g.Te, 1);
   }
   return true;
 }
@@ -248,6 +288,7 @@ struct Model {
   std::vector<InfStep> inf;
   std::vector<EncStep> enc;
   std::vector<GenStep> gen;
+  std::vector<FlatStep> flat;
   long long n_total = 0, n_live = 0, phi_stride = 0;
   // gradient buckets in backward completion order: theta of step t = [step_lo[t], step_hi[t]),
   // all recognition weights = [0, phi_hi) (parallel.step_buckets restates these)
@@ -282,6 +323,7 @@ struct Model {
     if (g.share_phi && swap("phi/inference_step_", "phi/inference_network", g.plc ? 1 : 0, o)) return o;
     if (g.share_theta && swap("theta/generative_encoder_step_", "theta/generative_encoder_network", 0, o)) return o;
     if (g.share_theta && swap("theta/generative_step_", "theta/generative_network", 1, o)) return o;
+    if (g.share_theta && swap("theta/generative_flat_step_", "theta/generative_network_flat", 1, o)) return o;  // :1919-1923
     return n;
   }
 
@@ -333,6 +375,7 @@ struct Model {
     inf.assign(g.T, InfStep());
     enc.assign(g.T, EncStep());
     gen.assign(g.T, GenStep());
+    flat.assign(g.T, FlatStep());
     for (int t = 0; t < g.T; ++t) {
       // phi/inference_step_t  (sequential_vae.py:1579-1609)
       Scope sc{"phi/inference_step_" + std::to_string(t), &descs, R_PHI, t};
@@ -362,6 +405,13 @@ struct Model {
       sc.fc(h.nin, h.d, h.wm, h.bm);
       sc.fc(h.nin, h.d, h.ws, h.bs);
       // theta/generative_encoder_step_t  (:1764-1775); steps t >= Te have no encoder / generator here
+      if (g.flat && t >= 1) {
+        // theta/generative_flat_step_t (:1919-1929): Conv .. Conv_{nl-2} + BatchNorm.., then Conv_{nl-1}
+        Scope sf{"theta/generative_flat_step_" + std::to_string(t), &descs, R_THETA, t};
+        FlatStep& Fs = flat[t];
+        for (int l = 0; l < g.fl_nl - 1; ++l) Fs.l[l] = sf.conv_bn(g.fl_F[l], g.fl_F[l + 1], 1, g.H, false);
+        sf.conv_plain(4, g.fl_F[g.fl_nl - 1], g.C, Fs.wout, Fs.bout);
+      }
       if (t >= g.Te) continue;
       if (t >= 1) {
         Scope se{"theta/generative_encoder_step_" + std::to_string(t), &descs, R_THETA, t};
@@ -432,6 +482,8 @@ struct Model {
       G.owout = off(G.wout); G.obout = off(G.bout); G.owratio = off(G.wratio); G.obratio = off(G.bratio);
       for (int l = 0; l < g.sd_nl; ++l) rc(G.sd[l]);
       G.owsd = off(G.wsd); G.obsd = off(G.bsd);
+      for (int l = 0; l < g.fl_nl - 1; ++l) rc(flat[t].l[l]);
+      flat[t].owout = off(flat[t].wout); flat[t].obout = off(flat[t].bout);
     }
   }
 };
@@ -600,6 +652,8 @@ struct svae_ctx {
     bool has_sample;
     float *sample, *sd;
     float *sd_pre[8], *sd_act[8], *sd_mean[8], *sd_inv[8];
+    // flat generator step: the pre-BN tensor and statistics of every conv_bn layer (the only saved state)
+    float *fl_pre[8], *fl_mean[8], *fl_inv[8];
   };
   std::vector<StepBufs> sb;
   int out_nblk = 0;
@@ -616,6 +670,9 @@ struct svae_ctx {
   float *sd_d[2] = {}, *sd_dpre = nullptr, *sd_wpart = nullptr, *sd_sums = nullptr, *dmle = nullptr;
   double* sd_part = nullptr;
   float *dseed = nullptr, *imp_img = nullptr, *kl_zero = nullptr;
+  // flat generator: dz ping-pong, fp64 reduce partials, BN-backward sums, weight-gradient slabs
+  float *fl_dz[2] = {}, *fl_sums[2] = {}, *fl_wpart = nullptr;
+  double* fl_part = nullptr;
   bool imp_pass = false;             // svae_backward_imp: seeds from the improvement loss only
   // external generator steps (Geo::Te < T): the caller's d loss / d x_hat_{Te-1} [B,H,W,C] and
   // d loss / d z [T,B,Dz] (rows t >= Te) for the next backward (svae_set_external_grads, one-shot)
@@ -1773,6 +1830,96 @@ static void sd_backward_input(svae_ctx* c, int t) {
                 g.C + 1, 1, c->st);
 }
 
+// generator_flat of step t >= 1 (:1906-1935) on training_samples[t-1]: one launch per layer plus its
+// statistics' finish; the next layer stages lrelu(bn(pre)) itself, so no activated tensor is stored.
+// The output conv writes a_out (ld C+1, as the ladder's packed output) for output_fwd without a highway.
+static int flat_forward(svae_ctx* c, int t) {
+  const Geo& g = c->m.g;
+  const FlatStep& Fs = c->m.flat[t];
+  svae_ctx::StepBufs& s = c->sb[t];
+  hipStream_t st = c->st;
+  const long long P = (long long)g.B * g.H * g.W;
+  const int nblk = flat_blocks(g.B, g.H), nl = g.fl_nl;
+  FlatIn in;
+  in.p = chain_x(c, t - 1);
+  for (int l = 0; l < nl - 1; ++l) {
+    const int Ci = g.fl_F[l], Co = g.fl_F[l + 1];
+    if (flat_conv(in, g.B, g.H, Ci, c->P + Fs.l[l].ow, Co, 0, nullptr, s.fl_pre[l], Co, FlatOut{}, c->fl_part, st))
+      return fail(c, SVAE_EBADCONFIG, "flat_generator: layer does not fit the LDS window");
+    sd_stat_fin(c->fl_part, nblk, Co, P, 1e-3f, 0, s.fl_mean[l], s.fl_inv[l], nullptr, nullptr, st);
+    in = FlatIn{};
+    in.p = s.fl_pre[l]; in.mode = 1;
+    in.mean = s.fl_mean[l]; in.invstd = s.fl_inv[l]; in.beta = c->P + Fs.l[l].obeta;
+  }
+  if (flat_conv(in, g.B, g.H, g.fl_F[nl - 1], c->P + Fs.owout, g.C, 0, c->P + Fs.obout, s.a_out, g.C + 1, FlatOut{},
+                nullptr, st))
+    return fail(c, SVAE_EBADCONFIG, "flat_generator: layer does not fit the LDS window");
+  output_fwd(s.a_out, g.B, g.H * g.W, g.C, nullptr, c->tgt_in, g.lo, g.hi, g.minh, g.maxh, s.xhat, s.rec_part,
+             c->out_nblk, st);
+  const long long nimg = P * g.C;
+  if (s.has_sample) chain_noise(s.xhat, c->noise_used + t * nimg, c->reg * g.nstd[t], nimg, s.sample, st);
+  loss_reduce(s.rec_part, c->out_nblk, c->kl_img + (long long)t * g.B, g.B, g.H * g.W * g.C, s.stats, s.rec_img, st);
+  return 0;
+}
+
+// backward of flat_forward.  dxin = d loss / d training_samples[t] (null: none), dxout = d loss /
+// d training_samples[t-1].  Per conv_bn layer: its statistics' finish, the weight gradient (+ slab sum)
+// and the input gradient, whose epilogue forms dz and the BN-backward partials of the layer below;
+// d pre is formed while staging (FlatIn mode 2), never stored.
+static int flat_backward(svae_ctx* c, int t, const float* dxin, float rec_coef, float* dxout) {
+  const Geo& g = c->m.g;
+  const FlatStep& Fs = c->m.flat[t];
+  svae_ctx::StepBufs& s = c->sb[t];
+  hipStream_t st = c->st;
+  const int C1 = g.C + 1;
+  const long long P = (long long)g.B * g.H * g.W;
+  const int nblk = flat_blocks(g.B, g.H), nl = g.fl_nl;
+  const char* nofit = "flat_generator: layer does not fit the LDS window";
+  output_bwd(s.a_out, g.B, g.H * g.W, g.C, nullptr, s.xhat, c->tgt_in, g.lo, g.hi, g.minh, g.maxh, rec_coef, dxin, c->da,
+             nullptr, st);
+  // output bias gradient: column sums of da
+  flat_colsum(c->da, C1, P, g.C, c->fl_part, st);
+  sd_stat_fin(c->fl_part, flat_colsum_blocks(P), g.C, P, 0.f, 1, nullptr, nullptr, c->fl_sums[0], c->Gr + Fs.obout, st);
+  auto act_in = [&](int l) {  // the input of layer l: the chain sample, or lrelu(bn(pre)) of layer l - 1
+    FlatIn in;
+    if (l == 0) {
+      in.p = chain_x(c, t - 1);
+    } else {
+      in.p = s.fl_pre[l - 1]; in.mode = 1;
+      in.mean = s.fl_mean[l - 1]; in.invstd = s.fl_inv[l - 1]; in.beta = c->P + Fs.l[l - 1].obeta;
+    }
+    return in;
+  };
+  auto below = [&](int l) {  // the epilogue of layer l's input gradient: BN + lrelu of layer l - 1
+    FlatOut o;
+    if (l > 0) {
+      o.pre = s.fl_pre[l - 1]; o.mean = s.fl_mean[l - 1]; o.invstd = s.fl_inv[l - 1]; o.beta = c->P + Fs.l[l - 1].obeta;
+    }
+    return o;
+  };
+  int cur = 0;
+  FlatIn dy;
+  dy.p = c->da; dy.ld = C1;
+  for (int l = nl - 1; l >= 0; --l) {
+    const int Ci = g.fl_F[l], Co = g.fl_F[l + 1];
+    const float* W = c->P + (l == nl - 1 ? Fs.owout : Fs.l[l].ow);
+    float* dW = c->Gr + (l == nl - 1 ? Fs.owout : Fs.l[l].ow);
+    if (l < nl - 1) {  // (S, Q) of this layer's dz partials, dbeta = S; d pre on the load from here on
+      sd_stat_fin(c->fl_part, nblk, Co, P, 0.f, 1, nullptr, nullptr, c->fl_sums[cur], c->Gr + Fs.l[l].obeta, st);
+      dy = FlatIn{};
+      dy.p = c->fl_dz[cur]; dy.mode = 2;
+      dy.pre = s.fl_pre[l]; dy.mean = s.fl_mean[l]; dy.invstd = s.fl_inv[l]; dy.sums = c->fl_sums[cur];
+      dy.inv_n = 1.f / (float)P;
+    }
+    if (flat_wgrad(act_in(l), dy, g.B, g.H, Ci, Co, c->fl_wpart, dW, st)) return fail(c, SVAE_EBADCONFIG, nofit);
+    float* dst = l > 0 ? c->fl_dz[cur ^ 1] : dxout;
+    if (flat_conv(dy, g.B, g.H, Co, W, Ci, 1, nullptr, dst, Ci, below(l), l > 0 ? c->fl_part : nullptr, st))
+      return fail(c, SVAE_EBADCONFIG, nofit);
+    cur ^= 1;
+  }
+  return 0;
+}
+
 // ============================================================================
 // forward
 // ============================================================================
@@ -1881,6 +2028,10 @@ static int engine_forward(svae_ctx* c) {
   for (int t = 0; t < T; ++t) {
     svae_ctx::StepBufs& s = c->sb[t];
     if (t == 1 && rsplit) hipStreamWaitEvent(st, c->ev_rs2, 0);  // recognition of steps >= 1 (st4)
+    if (g.flat && t >= 1) {  // flat generator step: no encoder, split-latent or ladder
+      if ((r = flat_forward(c, t))) return r;
+      continue;
+    }
     if (t >= g.Te) {  // external generator step: only its KL statistics here (recon 0: the caller's)
       HIPCHK(c, hipMemsetAsync(s.rec_part, 0, (size_t)B * c->out_nblk * sizeof(float), st));
       loss_reduce(s.rec_part, c->out_nblk, c->kl_img + (long long)t * B, B, g.H * g.W * g.C, s.stats, s.rec_img, st);
@@ -2136,6 +2287,16 @@ static int engine_backward_pass(svae_ctx* c) {
     // the previous pass's readers were joined into this stream: every per-pass region is free
     c->dpre_off = c->idpre_off = c->dcat_off = c->dtop_off = 0;
   }
+  if (g.flat) {  // the flat steps T-1 .. 1; z_t of these steps reaches the loss through its KL term only
+    for (int t = T - 1; t >= 1; --t) {
+      if (t < T - 1 && (r = step_hook(c, t + 1))) return r;  // step t+1's gradients are complete
+      if (t < c->dbg_stop_step) return 0;
+      const float rec_coef = (g.interm || t == T - 1) ? 16.f / (float)(P0 * g.C) : 0.f;
+      c->da = c->da_base + (long long)t * P0 * C1;
+      if ((r = flat_backward(c, t, t < T - 1 ? c->dx[t & 1] : nullptr, rec_coef, c->dx[(t - 1) & 1]))) return r;
+    }
+    if (T > 1 && (r = step_hook(c, 1))) return r;
+  }
   for (int t = g.Te - 1; t >= 0; --t) {
     if (t < g.Te - 1) {
       if (g.plc) {  // q(z_{t+1} | x_t): its weights' gradients and its share of d loss / d x_t
@@ -2150,7 +2311,7 @@ static int engine_backward_pass(svae_ctx* c) {
     const float* xprev = t >= 1 ? chain_x(c, t - 1) : nullptr;
     // d loss / d training_samples[t]: from step t+1's backward, or for the last internal step from
     // the external generator (svae_set_external_grads)
-    const float* dxin = t < g.Te - 1 ? c->dx[t & 1] : (g.Te < T ? c->ext_dx : nullptr);
+    const float* dxin = t < g.Te - 1 ? c->dx[t & 1] : (g.Te < T ? (g.flat ? c->dx[t & 1] : c->ext_dx) : nullptr);
     float* dxout = t >= 1 ? c->dx[(t - 1) & 1] : nullptr;
     const float cf = t == 0 ? g.c_first : 1.f;
     float rec_coef = (g.interm || t == T - 1) ? 16.f * cf / (float)(P0 * g.C) : 0.f;
@@ -2501,7 +2662,8 @@ static bool plan(svae_ctx* c) {
   for (int t = 0; t < T; ++t) {
     svae_ctx::StepBufs& s = c->sb[t];
     memset(&s, 0, sizeof(s));
-    if (t >= 1) {
+    const bool ladder = !(g.flat && t >= 1);  // a flat step has no encoder / decoder tensors
+    if (t >= 1 && ladder) {
       for (int lvl = 0; lvl < L - 1; ++lvl) {
         long long n = (long long)B * S[lvl + 1] * S[lvl + 1] * F[lvl + 1];
         s.enc_pre_a[lvl] = A(n); s.enc_act_a[lvl] = A(n); s.enc_pre_b[lvl] = A(n); s.enc_act_b[lvl] = A(n);
@@ -2511,7 +2673,7 @@ static bool plan(svae_ctx* c) {
       s.enc_c_pre = A(nc); s.enc_c_act = A(nc); s.enc_bn_c = bn(1, F[L - 1]);
       s.encfc_pre = A((long long)B * F[L]); s.enc_bn_fc = bn(1, F[L]);
     }
-    for (int i = 0; i < L; ++i) {
+    for (int i = 0; i < L && ladder; ++i) {
       int J = c->m.gen[t].split[i].nout;
       maxJ = std::max<long long>(maxJ, J);
       maxK = std::max(maxK, g.D[i]);
@@ -2519,11 +2681,13 @@ static bool plan(svae_ctx* c) {
       s.split_inv[i] = A(J);
     }
     s.ktop = F[L + 1] + (t >= 1 ? F[L] : 0);
-    s.top_cat = A((long long)B * s.ktop);
     long long ntop = (long long)B * S[L] * S[L] * F[L];
-    s.top_pre = A(ntop); s.top_act = A(ntop); s.top_bn = bn(1, S[L] * S[L] * F[L]);
+    if (ladder) {
+      s.top_cat = A((long long)B * s.ktop);
+      s.top_pre = A(ntop); s.top_act = A(ntop); s.top_bn = bn(1, S[L] * S[L] * F[L]);
+    }
     maxact = std::max(maxact, ntop);
-    for (int lvl = 0; lvl < L - 1; ++lvl) {
+    for (int lvl = 0; lvl < L - 1 && ladder; ++lvl) {
       long long n = (long long)B * S[lvl + 1] * S[lvl + 1] * F[lvl + 1];
       s.s2_pre[lvl] = A(n); s.cat[lvl] = A(2 * n); s.s1_pre[lvl] = A(n); s.s1_act[lvl] = A(n);
       s.s2_bn[lvl] = bn(1, F[lvl + 1]); s.s1_bn[lvl] = bn(1, F[lvl + 1]);
@@ -2550,6 +2714,13 @@ static bool plan(svae_ctx* c) {
         s.sd_inv[l] = A(Co);
       }
     }
+    if (!ladder)
+      for (int l = 0; l < g.fl_nl - 1; ++l) {
+        const int Co = g.fl_F[l + 1];
+        s.fl_pre[l] = A(npx * Co);
+        s.fl_mean[l] = A(Co);
+        s.fl_inv[l] = A(Co);
+      }
   }
   {
     const long long npx = (long long)B * g.H * g.W;
@@ -2561,6 +2732,20 @@ static bool plan(svae_ctx* c) {
       c->sd_wpart = A(std::max<long long>((long long)sd_wgrad_blocks(B, g.H) * 16 * 64, 9LL * sd_pixel_blocks(npx)));
       c->sd_sums = A(16);
       c->dmle = A(npx * g.C);
+    }
+    if (g.flat) {
+      long long wmax = 0;
+      int cmax = 1;
+      for (int l = 0; l < g.fl_nl; ++l) {
+        wmax = std::max(wmax, 16LL * g.fl_F[l] * g.fl_F[l + 1]);
+        cmax = std::max(cmax, g.fl_F[l]);
+      }
+      for (int i = 0; i < 2; ++i) {
+        c->fl_dz[i] = A(npx * cmax);  // dz of a conv_bn layer's output: fl_F[1 .. nl-1] channels
+        c->fl_sums[i] = A(64);
+      }
+      c->fl_part = (double*)A(2LL * std::max(flat_blocks(B, g.H), flat_colsum_blocks(npx)) * 2 * 32);
+      c->fl_wpart = A((long long)flat_blocks(B, g.H) * wmax);
     }
     if (g.imp) {
       c->dseed = A(npx * g.C);
@@ -3048,7 +3233,7 @@ int svae_generate(svae_ctx* c, const float* z, void* stream) {
 
 int svae_set_external_grads(svae_ctx* c, const float* dxhat, const float* dz) {
   if (!c) return fail(c, SVAE_EBADARG, "null ctx");
-  if (c->m.g.Te == c->m.g.T && (dxhat || dz)) return fail(c, SVAE_EBADARG, "external_generator_from is off");
+  if ((c->m.g.Te == c->m.g.T || c->m.g.flat) && (dxhat || dz)) return fail(c, SVAE_EBADARG, "external_generator_from is off");
   c->ext_dx = dxhat;
   c->ext_dz = dz;
   return 0;
@@ -3416,6 +3601,54 @@ int svae_op_bn_act_bwd(const float* dy, const float* y, const float* x, int64_t 
   int r = bn_act_bwd(&dummy, 1, rows, c, View{(float*)dy, c, 0}, View{(float*)y, c, 0}, x, 0, c, bn, 0, 0, 0, act, dx,
                      0, View{}, 0);
   if (r) return fail(nullptr, r, dummy.err);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
+}
+
+int svae_op_flat_conv(const float* x, int n, int h, int cin, const float* w, int cout, const float* in_mean,
+                      const float* in_invstd, const float* in_beta, float* y, float* stats_out, void* stream) {
+  if (!x || !w || !y || ((in_mean != nullptr) != (in_invstd != nullptr)) || ((in_mean != nullptr) != (in_beta != nullptr)))
+    return fail(nullptr, SVAE_EBADARG, "bad op args");
+  if (!flat_conv_ok(n, h, cin, cout)) return fail(nullptr, SVAE_EBADCONFIG, "flat conv: channels in [1,32] and an LDS window that fits");
+  hipStream_t s = (hipStream_t)stream;
+  // the statistics' block partials: a scratch of this entry point (the engine's is planned in its arena)
+  static double* part = nullptr;
+  static long long part_cap = 0;
+  const long long need = (long long)flat_blocks(n, h) * 2 * cout;
+  if (stats_out && need > part_cap) {
+    if (part) { hipDeviceSynchronize(); hipFree(part); part = nullptr; part_cap = 0; }
+    if (hipMalloc((void**)&part, (size_t)need * sizeof(double)) != hipSuccess) return fail(nullptr, SVAE_ENOMEM, "hipMalloc");
+    part_cap = need;
+  }
+  FlatIn in;
+  in.p = x;
+  if (in_mean) { in.mode = 1; in.mean = in_mean; in.invstd = in_invstd; in.beta = in_beta; }
+  flat_conv(in, n, h, cin, w, cout, 0, nullptr, y, cout, FlatOut{}, stats_out ? part : nullptr, s);
+  if (stats_out) sd_stat_fin(part, flat_blocks(n, h), cout, 1, 0.f, 1, nullptr, nullptr, stats_out, nullptr, s);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
+}
+
+int svae_op_flat_dgrad(const float* dy, int n, int h, int cin, const float* w, int cout, float* dx, void* stream) {
+  if (!dy || !w || !dx) return fail(nullptr, SVAE_EBADARG, "bad op args");
+  if (!flat_conv_ok(n, h, cout, cin)) return fail(nullptr, SVAE_EBADCONFIG, "flat dgrad: channels in [1,32] and an LDS window that fits");
+  FlatIn in;
+  in.p = dy;
+  flat_conv(in, n, h, cout, w, cin, 1, nullptr, dx, cin, FlatOut{}, nullptr, (hipStream_t)stream);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
+}
+
+int svae_op_flat_wgrad(const float* x, int n, int h, int cin, const float* dy, int cout, float* dw, void* scratch,
+                       int64_t scratch_bytes, void* stream) {
+  if (!x || !dy || !dw || !scratch) return fail(nullptr, SVAE_EBADARG, "bad op args");
+  if (!flat_wgrad_ok(n, h, cin, cout)) return fail(nullptr, SVAE_EBADCONFIG, "flat wgrad: channels in [1,32] and an LDS window that fits");
+  if ((int64_t)flat_blocks(n, h) * 16 * cin * cout * (int64_t)sizeof(float) > scratch_bytes)
+    return fail(nullptr, SVAE_EBADARG, "scratch too small");
+  FlatIn in, d;
+  in.p = x;
+  d.p = dy;
+  flat_wgrad(in, d, n, h, cin, cout, (float*)scratch, dw, (hipStream_t)stream);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
 }

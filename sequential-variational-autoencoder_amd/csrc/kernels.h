@@ -366,3 +366,31 @@ void imp_seed(const float* dxin, const float* xp, const float* x, const float* x
               hipStream_t s);
 // out[b] = ||a_b - b_b||^2 per image
 void sqdiff_img(const float* a, const float* b, int B, long long per_img, float* out, hipStream_t s);
+
+// ---- flat-convolution generator (flat.hip): 4x4 stride-1 TF-SAME convs, <= 32 channels, fp32 MFMA ----
+// A tensor as the kernels stage it.  mode 0: p [N,H,W,ld] as it is; mode 1: lrelu(bn(p)) with the
+// producer's mean / invstd / beta (zeros pad the activated tensor); mode 2: p is dz = d act * lrelu'(y)
+// and the staged value is d pre = invstd * (dz - S/n - xhat * Q/n), xhat from pre, (S, Q) = sums[2c..]
+struct FlatIn {
+  const float* p = nullptr;
+  int ld = 0;  // 0 = the channel count
+  int mode = 0;
+  const float *pre = nullptr, *mean = nullptr, *invstd = nullptr, *beta = nullptr, *sums = nullptr;
+  float inv_n = 0.f;
+};
+// input-gradient epilogue: dst = acc * lrelu'(bn(pre)) and the (sum dz, sum dz * xhat) partials
+struct FlatOut {
+  const float *pre = nullptr, *mean = nullptr, *invstd = nullptr, *beta = nullptr;
+};
+int flat_blocks(int N, int H);  // blocks of a launch = rows of the fp64 partials [blocks][C][2]
+bool flat_conv_ok(int N, int H, int Cs, int Cd);   // shape limits and the LDS window fit
+bool flat_wgrad_ok(int N, int H, int Ci, int Co);
+// adj 0: dst[p*ldd + co] = conv(in, W) + bias, partials (sum, sum^2); adj 1: the input gradient of that conv
+// on in = d pre (Cs = Cout, Cd = Cin).  W is the TF tensor [4,4,Cin,Cout].  Returns -1 if the shape does not fit.
+int flat_conv(const FlatIn& in, int N, int H, int Cs, const float* W, int Cd, int adj, const float* bias, float* dst,
+              int ldd, const FlatOut& o, double* part, hipStream_t s);
+// dW [4,4,Ci,Co] = sum_pixels window(in) * dy; part: flat_blocks * 16*Ci*Co floats, summed in block order
+int flat_wgrad(const FlatIn& in, const FlatIn& dy, int N, int H, int Ci, int Co, float* part, float* dW, hipStream_t s);
+// per-block column sums of X [rows][ld] into fp64 partials [flat_colsum_blocks][C][2] (sd_stat_fin mode 1 finishes)
+int flat_colsum_blocks(long long rows);
+void flat_colsum(const float* X, int ld, long long rows, int C, double* part, hipStream_t s);

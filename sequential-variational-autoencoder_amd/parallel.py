@@ -34,7 +34,7 @@ def allreduce_hook(dist, group=None, bucket_elems=None):
     return hook
 
 
-_STEP = re.compile(r"^theta/generative(?:_encoder)?_step_(\d+)/")
+_STEP = re.compile(r"^theta/generative(?:_encoder|_flat)?_step_(\d+)/")
 
 
 def step_buckets(table, n_live):

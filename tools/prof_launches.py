@@ -11,7 +11,7 @@ from collections import defaultdict
 
 
 def short(n):
-    n = n.replace("void ", "")
+    n = n.replace("void ", "").replace("(anonymous namespace)::", "")
     return n.split("(")[0][:48]
 
 
@@ -42,7 +42,7 @@ def main():
                                                                gz // max(wz, 1), us))
     print("\nstep: %d launches, span %.1f us, kernel-busy %.1f us (%.1f%%)" % (len(step), span, busy,
                                                                                100 * busy / span))
-    for k, v in sorted(tot.items(), key=lambda kv: -kv[1])[:25]:
+    for k, v in sorted(tot.items(), key=lambda kv: -kv[1])[:40]:
         print("  %-48s %5d  %9.1f us" % (k, cnt[k], v))
 
 
