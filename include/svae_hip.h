@@ -266,6 +266,25 @@ int svae_op_bn_act_bwd(const float* dy, const float* y, const float* x, int64_t 
                        void* stream);
 /* y[B,N] = x[B,K] @ w[K,N]  (fully_connected, no bias) */
 int svae_op_fc(const float* x, int b, int k, const float* w, int nout, float* y, void* stream);
+/* The training batch in one launch on `stream` (no allocation, no synchronisation): rows of a
+ * device-resident dataset data [N, per_image] (uint8 when data_u8 = 1, else fp32) are gathered,
+ * dequantised into the clean `target` and corrupted into the denoising `input`, both [n, per_image]
+ * fp32; either may be NULL, not both.  Row b is data[idx[b]], or data[start + b] when idx == NULL
+ * (indices are the caller's contract: no device-side check).
+ *   target = lo + u8 * ((hi - lo) / 255)            (fp32 rows: the row as it is)
+ *   input  = clip(target * keep + salt + gaussian_scale * N(0,1), lo, hi)
+ * keep is 0 with probability pepper_prob and salt is 1 with probability salt_prob (pepper multiplies by
+ * 0, salt ADDS 1: the reference's apply_noise as written).  Draws are Philox4x32-10 with key
+ * (lo32(seed), hi32(seed)): flat output element e uses counter offset + e / 4 in words (c0, c1), c3 = 0,
+ * and c2 = 0 for the four normals (Box-Muller on words (0,1) and (2,3) -> lanes 0..3), c2 = 1 for the
+ * pepper words (keep_j = w_j >= thr(pepper_prob)), c2 = 2 for the salt words (salt_j = w_j <
+ * thr(salt_prob)), thr(p) = min(floor(p * 2^32), 2^32 - 1).  The result depends on no launch geometry;
+ * a caller advances offset by ceil(n * per_image / 4) per call.  In place (input == data) is allowed
+ * for fp32 data with idx == NULL and start == 0.  SVAE_EBADARG: null data, both outputs null, n or
+ * per_image <= 0, a probability outside [0, 1], a negative scale, lo > hi. */
+int svae_op_make_batch(const void* data, int data_u8, const int32_t* idx, int64_t start, int n, int64_t per_image,
+                       float lo, float hi, float pepper_prob, float salt_prob, float gaussian_scale, uint64_t seed,
+                       uint64_t offset, float* target, float* input, void* stream);
 
 #ifdef __cplusplus
 }

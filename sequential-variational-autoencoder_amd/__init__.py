@@ -14,6 +14,12 @@ def __getattr__(name):
     if name == "SequentialVAE":
         from .sequential_vae import SequentialVAE
         return SequentialVAE
+    if name == "NoisyTrainer":
+        from .trainer import NoisyTrainer
+        return NoisyTrainer
+    if name == "DeviceDataset":
+        from .data import DeviceDataset
+        return DeviceDataset
     if name == "parallel":
         from . import parallel
         return parallel

@@ -1,0 +1,167 @@
+// The training batch in one launch: gather rows of a device-resident dataset (uint8 or fp32), dequantise
+// into the clean target, and corrupt a copy into the denoising input (the reference's apply_noise,
+// trainer.py:71-78: pepper multiplies by 0, salt adds 1, Gaussian noise, clip to the data range).
+//
+// Random draws are counter-based (philox.h): flat output element e of the [n * per_image] batch belongs to
+// group g = e / 4, lane j = e % 4; the 64-bit counter offset + g fills c0 / c1, c3 = 0 and c2 selects the
+// stream (0 normals, 1 pepper word, 2 salt word).  Nothing depends on the launch geometry or on the path
+// (vector / scalar) the alignment selects.
+#include <cstdint>
+
+#include "common.h"
+#include "kernels.h"
+#include "philox.h"
+
+namespace {
+
+constexpr int MB_THREADS = 256;
+constexpr int MB_TILE = MB_THREADS * 16;  // elements of one uint8 tile: one 16-byte load per lane
+
+// the four outputs of group g from its four clean values
+__device__ __forceinline__ void mb_corrupt(const float t[4], long long g, const MakeBatchArgs& a, float o[4]) {
+#pragma clang fp contract(off)
+  const unsigned long long ctr = a.offset + (unsigned long long)g;
+  const unsigned lo32 = (unsigned)ctr, hi32 = (unsigned)(ctr >> 32);
+  const unsigned k0 = (unsigned)a.seed, k1 = (unsigned)(a.seed >> 32);
+  float nrm[4] = {0.f, 0.f, 0.f, 0.f};
+  unsigned pw[4] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};  // keep (thr_pepper = 0: every word keeps)
+  unsigned sw[4] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};  // no salt (thr_salt = 0: no word salts)
+  if (a.scale != 0.f) {  // the normals are finite, so a zero scale adds exactly +-0
+    unsigned c0 = lo32, c1 = hi32, c2 = 0, c3 = 0;
+    philox(c0, c1, c2, c3, k0, k1);
+    philox_box_muller(c0, c1, c2, c3, nrm);
+  }
+  if (a.thr_pepper) {
+    pw[0] = lo32; pw[1] = hi32; pw[2] = 1; pw[3] = 0;
+    philox(pw[0], pw[1], pw[2], pw[3], k0, k1);
+  }
+  if (a.thr_salt) {
+    sw[0] = lo32; sw[1] = hi32; sw[2] = 2; sw[3] = 0;
+    philox(sw[0], sw[1], sw[2], sw[3], k0, k1);
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float keep = pw[j] >= a.thr_pepper ? 1.f : 0.f;
+    const float salt = sw[j] < a.thr_salt ? 1.f : 0.f;
+    // each operation rounded on its own (contract(off) above), in the order the contract states
+    float v = t[j] * keep + salt;
+    const float gn = a.scale * nrm[j];
+    v = v + gn;
+    o[j] = fminf(fmaxf(v, a.lo), a.hi);
+  }
+}
+
+// lo + q * qscale with the product and the sum each rounded to fp32 (the *_rn intrinsics are plain operators
+// to the compiler, which would contract them into one fma: the pragma keeps the two roundings the contract states)
+__device__ __forceinline__ float mb_dequant(unsigned char q, const MakeBatchArgs& a) {
+#pragma clang fp contract(off)
+  const float p = (float)q * a.qscale;
+  return a.lo + p;
+}
+
+__device__ __forceinline__ long long mb_row(const MakeBatchArgs& a, long long b) {
+  return a.idx ? (long long)a.idx[b] : a.start + b;
+}
+
+// fp32 rows, per_image % 4 == 0, every pointer 16-byte aligned: one group per lane, 16-byte load and stores
+__global__ __launch_bounds__(MB_THREADS) void make_batch_f32v_kernel(MakeBatchArgs a) {
+  const long long G = a.total >> 2;
+  const float* __restrict__ data = (const float*)a.data;
+  for (long long g = (long long)blockIdx.x * MB_THREADS + threadIdx.x; g < G; g += (long long)gridDim.x * MB_THREADS) {
+    const long long e = g << 2;
+    const long long b = e / a.per_image, off = e - b * a.per_image;
+    const float4 x = *reinterpret_cast<const float4*>(data + mb_row(a, b) * a.per_image + off);
+    const float t[4] = {x.x, x.y, x.z, x.w};
+    if (a.input) {  // in place (input == data) is safe: the lane has read what it overwrites
+      float o[4];
+      mb_corrupt(t, g, a, o);
+      *reinterpret_cast<float4*>(a.input + e) = make_float4(o[0], o[1], o[2], o[3]);
+    }
+    if (a.target) *reinterpret_cast<float4*>(a.target + e) = x;
+  }
+}
+
+// uint8 rows, per_image % 16 == 0, every pointer 16-byte aligned: a tile of 4096 pixels is staged through
+// LDS with one 16-byte load per lane (16 pixels), then lane l takes groups l, l + 256, ... of the tile so
+// that every store instruction of a wave covers 1 KiB of contiguous output
+__global__ __launch_bounds__(MB_THREADS) void make_batch_u8v_kernel(MakeBatchArgs a) {
+  __shared__ uint4 stage[MB_THREADS];
+  const unsigned char* __restrict__ data = (const unsigned char*)a.data;
+  const long long ntile = (a.total + MB_TILE - 1) / MB_TILE;
+  for (long long tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
+    const long long e0 = tile * MB_TILE + (long long)threadIdx.x * 16;
+    if (e0 < a.total) {  // total % 16 == 0: a 16-pixel chunk is whole, inside one row and aligned
+      const long long b = e0 / a.per_image, off = e0 - b * a.per_image;
+      stage[threadIdx.x] = *reinterpret_cast<const uint4*>(data + mb_row(a, b) * a.per_image + off);
+    }
+    __syncthreads();
+    const unsigned* words = reinterpret_cast<const unsigned*>(stage);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int q = k * MB_THREADS + threadIdx.x;
+      const long long e = tile * MB_TILE + (long long)q * 4;
+      if (e < a.total) {
+        const unsigned w = words[q];
+        const float t[4] = {mb_dequant((unsigned char)(w & 0xFF), a), mb_dequant((unsigned char)((w >> 8) & 0xFF), a),
+                            mb_dequant((unsigned char)((w >> 16) & 0xFF), a), mb_dequant((unsigned char)(w >> 24), a)};
+        if (a.input) {
+          float o[4];
+          mb_corrupt(t, e >> 2, a, o);
+          *reinterpret_cast<float4*>(a.input + e) = make_float4(o[0], o[1], o[2], o[3]);
+        }
+        if (a.target) *reinterpret_cast<float4*>(a.target + e) = make_float4(t[0], t[1], t[2], t[3]);
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// any per_image and alignment: one group per lane, element by element (groups may straddle rows; the last
+// group may be partial)
+template <bool U8>
+__global__ __launch_bounds__(MB_THREADS) void make_batch_scalar_kernel(MakeBatchArgs a) {
+  const long long G = (a.total + 3) >> 2;
+  for (long long g = (long long)blockIdx.x * MB_THREADS + threadIdx.x; g < G; g += (long long)gridDim.x * MB_THREADS) {
+    const long long e = g << 2;
+    long long b = e / a.per_image, off = e - b * a.per_image;
+    float t[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (e + j < a.total) {
+        const long long src = mb_row(a, b) * a.per_image + off;
+        t[j] = U8 ? mb_dequant(((const unsigned char*)a.data)[src], a) : ((const float*)a.data)[src];
+      }
+      if (++off == a.per_image) { off = 0; ++b; }
+    }
+    float o[4];
+    if (a.input) mb_corrupt(t, g, a, o);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (e + j < a.total) {
+        if (a.input) a.input[e + j] = o[j];
+        if (a.target) a.target[e + j] = t[j];
+      }
+  }
+}
+
+inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+}  // namespace
+
+void make_batch(const MakeBatchArgs& a, hipStream_t s) {
+  const bool al = al16(a.data) && al16(a.target) && al16(a.input);
+  const long long cap = 16384;  // grid-stride beyond this many blocks
+  if (a.data_u8 && al && a.per_image % 16 == 0) {
+    const long long nb = (a.total + MB_TILE - 1) / MB_TILE;
+    hipLaunchKernelGGL(make_batch_u8v_kernel, dim3((unsigned)(nb < cap ? nb : cap)), dim3(MB_THREADS), 0, s, a);
+    return;
+  }
+  const long long nb = ((a.total + 3) / 4 + MB_THREADS - 1) / MB_THREADS;
+  const dim3 grid((unsigned)(nb < cap ? nb : cap));
+  if (!a.data_u8 && al && a.per_image % 4 == 0)
+    hipLaunchKernelGGL(make_batch_f32v_kernel, grid, dim3(MB_THREADS), 0, s, a);
+  else if (a.data_u8)
+    hipLaunchKernelGGL(make_batch_scalar_kernel<true>, grid, dim3(MB_THREADS), 0, s, a);
+  else
+    hipLaunchKernelGGL(make_batch_scalar_kernel<false>, grid, dim3(MB_THREADS), 0, s, a);
+}

@@ -3667,4 +3667,39 @@ int svae_op_fc(const float* x, int b, int k, const float* w, int nout, float* y,
   return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
 }
 
+// thr(p) = min(floor(p 2^32), 2^32 - 1): a word w < thr(p) with probability p
+static uint32_t prob_threshold(float p) {
+  const double t = std::floor((double)p * 4294967296.0);
+  return t >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)t;
+}
+
+int svae_op_make_batch(const void* data, int data_u8, const int32_t* idx, int64_t start, int n, int64_t per_image,
+                       float lo, float hi, float pepper_prob, float salt_prob, float gaussian_scale, uint64_t seed,
+                       uint64_t offset, float* target, float* input, void* stream) {
+  if (!data) return fail(nullptr, SVAE_EBADARG, "make_batch: null data");
+  if (!target && !input) return fail(nullptr, SVAE_EBADARG, "make_batch: target and input are both null");
+  if (n <= 0 || per_image <= 0) return fail(nullptr, SVAE_EBADARG, "make_batch: n and per_image must be positive");
+  if (!(pepper_prob >= 0.f && pepper_prob <= 1.f) || !(salt_prob >= 0.f && salt_prob <= 1.f))
+    return fail(nullptr, SVAE_EBADARG, "make_batch: a probability outside [0, 1]");
+  if (!(gaussian_scale >= 0.f)) return fail(nullptr, SVAE_EBADARG, "make_batch: negative gaussian_scale");
+  if (!(lo <= hi)) return fail(nullptr, SVAE_EBADARG, "make_batch: lo > hi");
+  if (!idx && start < 0) return fail(nullptr, SVAE_EBADARG, "make_batch: negative start");
+  // in place: every lane overwrites exactly what it read, which holds only for the identity gather of fp32 rows
+  if (((const void*)input == data || (const void*)target == data) && (data_u8 || idx || start != 0))
+    return fail(nullptr, SVAE_EBADARG, "make_batch: in place needs fp32 data, idx == NULL and start == 0");
+  MakeBatchArgs a{};
+  a.data = data; a.data_u8 = data_u8 ? 1 : 0;
+  a.idx = idx; a.start = start;
+  a.per_image = per_image; a.total = (long long)n * per_image;
+  a.lo = lo; a.hi = hi;
+  a.qscale = (float)(((double)hi - (double)lo) / 255.0);
+  a.scale = gaussian_scale;
+  a.thr_pepper = prob_threshold(pepper_prob); a.thr_salt = prob_threshold(salt_prob);
+  a.seed = seed; a.offset = offset;
+  a.target = target; a.input = input;
+  make_batch(a, (hipStream_t)stream);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
+}
+
 }  // extern "C"

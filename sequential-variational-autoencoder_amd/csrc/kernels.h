@@ -327,6 +327,20 @@ int dense_kw(const FwdArgs& a, int ks, hipStream_t s);  // returns ks
 void bf16_to_f32(const void* src, float* dst, long long n, hipStream_t s);  // debug copies of bf16 activations
 void fill_f32(float* p, long long n, float v, hipStream_t s);
 void philox_normal(float* out, long long n, unsigned long long seed, unsigned long long offset, hipStream_t s);
+// ---- training batch (batch.hip): row gather + dequantisation + denoising corruption, one launch ----
+// row b of the batch = data[idx ? idx[b] : start + b] (uint8 or fp32 rows of per_image elements);
+// target = lo + u8 * qscale (fp32 rows: as they are); input = clip(target * keep + salt + scale * N(0,1), lo, hi)
+// with keep = (pepper word >= thr_pepper), salt = (salt word < thr_salt), Philox counters offset + e / 4
+struct MakeBatchArgs {
+  const void* data; int data_u8;
+  const int* idx; long long start;
+  long long per_image, total;        // total = n * per_image
+  float lo, hi, qscale, scale;       // qscale = (hi - lo) / 255
+  unsigned thr_pepper, thr_salt;
+  unsigned long long seed, offset;
+  float* target; float* input;       // either may be nullptr
+};
+void make_batch(const MakeBatchArgs& a, hipStream_t s);
 // column sums of X [rows][C<=4] -> out0[0..n0), out1[0..C-n0)   (part: scratch >= 1024 floats)
 void colsum_small(const float* X, int ld, long long rows, int C, float* part, float* out0, int n0, float* out1,
                   hipStream_t s);

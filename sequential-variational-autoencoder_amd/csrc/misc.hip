@@ -7,6 +7,7 @@
 #include "common.h"
 #include "knobs.h"
 #include "kernels.h"
+#include "philox.h"
 
 #define KMAX 32  // max latent dims per level handled in registers (LSUN: 30)
 
@@ -1440,33 +1441,15 @@ void fill_f32(float* p, long long n, float v, hipStream_t s) {
   hipLaunchKernelGGL(fill_kernel, dim3(ew_blocks(n)), dim3(256), 0, s, p, n, v);
 }
 
-// Philox4x32-10 -> Box-Muller normals (throughput-mode eps; parity mode injects eps)
-__device__ __forceinline__ void philox(unsigned& c0, unsigned& c1, unsigned& c2, unsigned& c3, unsigned k0,
-                                       unsigned k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    unsigned long long p0 = (unsigned long long)0xD2511F53u * c0;
-    unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c2;
-    unsigned h0 = (unsigned)(p0 >> 32), l0 = (unsigned)p0;
-    unsigned h1 = (unsigned)(p1 >> 32), l1 = (unsigned)p1;
-    unsigned n0 = h1 ^ c1 ^ k0, n2 = h0 ^ c3 ^ k1;
-    c0 = n0; c1 = l1; c2 = n2; c3 = l0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-}
-
+// Philox4x32-10 -> Box-Muller normals (philox.h; throughput-mode eps; parity mode injects eps)
 __global__ void philox_normal_kernel(float* out, long long n, unsigned long long seed, unsigned long long offset) {
   const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (q * 4 >= n) return;
   unsigned long long ctr = offset + q;
   unsigned c0 = (unsigned)ctr, c1 = (unsigned)(ctr >> 32), c2 = 0, c3 = 0;
   philox(c0, c1, c2, c3, (unsigned)seed, (unsigned)(seed >> 32));
-  const float inv = 2.3283064365386963e-10f;
-  float u0 = (c0 + 0.5f) * inv, u1 = (c1 + 0.5f) * inv, u2 = (c2 + 0.5f) * inv, u3 = (c3 + 0.5f) * inv;
-  float r0 = sqrtf(-2.f * __logf(u0)), r1 = sqrtf(-2.f * __logf(u2));
-  float v[4] = {r0 * __cosf(6.2831853f * u1), r0 * __sinf(6.2831853f * u1), r1 * __cosf(6.2831853f * u3),
-                r1 * __sinf(6.2831853f * u3)};
+  float v[4];
+  philox_box_muller(c0, c1, c2, c3, v);
   for (int e = 0; e < 4; ++e)
     if (q * 4 + e < n) out[q * 4 + e] = v[e];
 }

@@ -25,7 +25,9 @@ from .weights import init_flat, param_table, unflatten
 
 
 class SequentialVAE:
-    def __init__(self, config="celeba", batch_size=None, device=None, seed=0, grad_hook=None):
+    def __init__(self, config="celeba", batch_size=None, device=None, seed=0, grad_hook=None, share_params_with=None):
+        """share_params_with: another SequentialVAE whose ``params`` tensor this context reads (sibling());
+        the networks must agree in everything but the batch."""
         if not torch.cuda.is_available():
             raise RuntimeError("SequentialVAE (HIP engine) needs a GPU; no CPU fallback exists")
         cfg = preset(config) if isinstance(config, str) else config
@@ -43,8 +45,14 @@ class SequentialVAE:
         self.L = _lib.lib()
         self.table, self.n_total, self.n_live = param_table(cfg)
         self._by_name = {p["name"]: p for p in self.table}
+        self._owner = share_params_with
+        self._siblings = {}
+        if self._owner is not None and (preset_copy(self._owner.cfg, batch=cfg.batch) != cfg
+                                        or self._owner.device != self.device):
+            raise ValueError("a sibling differs from its owner in the batch only")
         with torch.cuda.device(self.device):
-            self.params = torch.from_numpy(init_flat(cfg, seed)).to(self.device)
+            self.params = (torch.from_numpy(init_flat(cfg, seed)).to(self.device) if self._owner is None
+                           else self._owner.params)
             self.grads = torch.zeros(self.n_total, dtype=torch.float32, device=self.device)
             h = ctypes.c_void_p()
             c = cfg.to_c()
@@ -88,6 +96,7 @@ class SequentialVAE:
         """Forward of the unrolled chain.  eps [T,B,Dz] or None (device Philox).  With
         add_noise_to_chain, noise [T,B,H,W,C] is the N(0,1) of training_sample = mle + reg*sd*noise
         (sequential_vae.py:1090), or None (device Philox)."""
+        self._sync_shared()
         x, target = self._dev(x), self._dev(target)
         nz = None
         if self.cfg.add_noise_to_chain:
@@ -282,6 +291,8 @@ class SequentialVAE:
         the same forward.  TF leaves their order open; here the ELBO update (all variables, Adam step
         2k-1) runs first and the improvement update (recognition variables, step 2k) second, sharing
         the Adam moments, so beta1_power advances twice per iteration as in TF."""
+        if self._owner is not None:
+            raise RuntimeError("a sibling context only reads its owner's parameters; train the owner")
         self.iteration += 1
         self.learning_rate *= self.cfg.learning_rate_decay
         reg = 1.0 - math.exp(-self.iteration / self.cfg.reg_coeff_rate)
@@ -373,6 +384,7 @@ class SequentialVAE:
         (sequential_vae.py:947-952, :1025).  With add_noise_to_chain, ``noise`` [T,B,H,W,C] injects
         the chain noise (None: drawn on device, never the last forward's).  Returns [x_hat_t]
         device tensors [B,H,W,C]."""
+        self._sync_shared()
         e = None
         if z is not None:
             e = self._dev(z)
@@ -402,6 +414,72 @@ class SequentialVAE:
         """training_mles[-1] for the batch (sequential_vae.py:1381-1391; reg_coeff default 1.0)."""
         self.forward(input_batch, input_batch, None, 1.0)
         return self.xhat(-1).cpu().numpy()
+
+    # ------------------------------------------------------------------ siblings / visualisation
+    def _sync_shared(self):
+        """A sibling reads parameters its owner's Adam writes behind this context's bf16 and shared-weight
+        copies: every forward / generate of a sibling first announces them (params_updated)."""
+        if self._owner is not None:
+            self.params_updated()
+
+    def sibling(self, batch_size):
+        """A second context at another batch that shares this network's ``params`` tensor (its own
+        gradients and arena): a context runs only the batch it was created for, and visualising or
+        testing at another batch must see the parameters training has reached.  Cached per batch; a
+        sibling does not train."""
+        owner = self if self._owner is None else self._owner
+        if batch_size == owner.cfg.batch:
+            return owner
+        s = owner._siblings.get(batch_size)
+        if s is None:
+            s = SequentialVAE(preset_copy(owner.cfg, batch=batch_size), device=owner.device.index,
+                              share_params_with=owner)
+            s.name = owner.name
+            owner._siblings[batch_size] = s
+        return s
+
+    def training_mc_samples(self, input_batch):
+        """Reference training_mc_samples (sequential_vae.py:1434-1455): the training branch's samples of the
+        batch as numpy arrays, [sample_0 .. sample_{T-1}]; under add_noise_to_chain the MLEs come first,
+        [mle_0 .. mle_{T-1}, sample_0 .. sample_{T-1}]."""
+        self.forward(input_batch, input_batch, None, 1.0)
+        T = self.cfg.mc_steps
+        out = [self.sample(t).cpu().numpy() for t in range(T)]
+        if self.cfg.add_noise_to_chain:
+            out = [self.xhat(t).cpu().numpy() for t in range(T)] + out
+        return out
+
+    def visualize(self, epoch, dataset, base_dir, batch_size=10):
+        """The reference's two chain pictures (sequential_vae.py:1461-1527) through a sibling context at
+        ``batch_size``: a generated chain (column 0 the U[0,1) start generate_mc_samples returns, then
+        x_hat_t) and a training chain (column 0 the input batch, then the samples); one row block per
+        image, two under add_noise_to_chain (MLEs above samples) -- canvas.chain_canvas.  Written to
+        <base_dir>/samples/{test,train}_epoch<epoch> and {test,train}_current; returns both canvases."""
+        from . import canvas as cv
+        net = self.sibling(batch_size)
+        T, noisy = self.cfg.mc_steps, self.cfg.add_noise_to_chain
+        disp = lambda a: dataset.display(np.asarray(a))
+        folder = None if base_dir is None else base_dir + "/samples"
+        out = []
+        for which in ("test", "train"):
+            if which == "test":
+                z = net.generate_mc_samples(None, batch_size)
+                start, mles = disp(z[0]), z[1:]
+                samples = [net.sample(t).cpu().numpy() for t in range(T)] if noisy else None
+            else:
+                bx = dataset.rows(dataset.next_batch(batch_size)).to(self.device)
+                if bx.dtype == torch.uint8:
+                    lo, hi = dataset.range
+                    bx = lo + bx.to(torch.float32) * ((hi - lo) / 255.0)
+                z = net.training_mc_samples(bx)
+                start = disp(bx.cpu().numpy())
+                mles, samples = (z[:T], z[T:]) if noisy else (z, None)
+            c = cv.chain_canvas(start, [disp(m) for m in mles], None if samples is None else [disp(s) for s in samples])
+            if folder is not None:
+                cv.save_canvas(c, folder, "%s_epoch%d" % (which, epoch))
+                cv.save_canvas(c, folder, "%s_current" % which)
+            out.append(c)
+        return out
 
 
 def preset_copy(cfg, **over):

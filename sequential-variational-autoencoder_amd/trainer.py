@@ -1,0 +1,187 @@
+"""The reference's NoisyTrainer (trainer.py) over a device-resident dataset.
+
+One training iteration is two enqueues: svae_op_make_batch (csrc/batch.hip) gathers the cursor's window from
+the dataset in HBM, dequantises it into the clean target and, with denoise_train, corrupts a copy into the
+input (pepper x0, salt +1, Gaussian, clip: trainer.py:71-78 on the device instead of three host draws over
+the batch in float64); then ``network.train(input, target)``.  Nothing crosses the host in the step but
+the returned loss.
+
+Draws are counter-based (Philox, key = seed, counter = offset): training noise and test noise use
+different seeds, each offset advances by ceil(B H W C / 4) per corrupted batch, and both are part of
+state_dict(), so a resumed run corrupts its next batch exactly as the uninterrupted run would.
+"""
+import json
+import logging
+import os
+import time
+
+import torch
+
+from . import _lib
+from . import canvas as cv
+
+
+class NoisyTrainer:
+    # the reference's class constants (trainer.py:16-21)
+    pepper_prob = 0.1
+    salt_prob = 0.1
+    gaussian_noise_scale = 0.1
+    max_training_iters = 10000000
+    test_num_iters = 5
+    log_loss_freq = 20
+    save_freq = 2000           # sequential_vae.py:254
+    test_seed_xor = 0x7E577E57A5A5A5A5  # test-noise key = seed ^ this
+
+    def __init__(self, network, dataset, denoise_train=False, vis_frequency=1000, plot_reconstruction=False,
+                 base_dir=None, logger=None, seed=0):
+        if list(dataset.data_dims) != list(network.data_dims):
+            raise ValueError("dataset images %s, network %s" % (dataset.data_dims, network.data_dims))
+        if tuple(dataset.range) != tuple(float(v) for v in network.cfg.range):
+            raise ValueError("dataset range %s, network %s" % (dataset.range, network.cfg.range))
+        if getattr(network.cfg, "external_generator_from", 0):
+            raise ValueError("the PixelVAE head is not a trainer network")
+        self.network = network
+        self.dataset = dataset
+        self.denoise_train = bool(denoise_train)
+        self.vis_frequency = int(vis_frequency)
+        self.plot_reconstruction_enabled = bool(plot_reconstruction)
+        self.base_dir = base_dir
+        self.LOG = logger if logger is not None else logging.getLogger("svae.trainer")
+        self.batch_size = network.batch_size
+        self.data_dims = list(dataset.data_dims)
+        self.device = network.device
+        if dataset.train.device != self.device or dataset.test.device != self.device:
+            raise ValueError("the dataset must live on the network's device (%s)" % self.device)
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.iteration = 0
+        self.train_offset = 0
+        self.test_offset = 0
+        shape = [self.batch_size] + self.data_dims
+        # one pair, reused: the kernel and the step that reads it are ordered on one stream
+        self._target = torch.empty(shape, dtype=torch.float32, device=self.device)
+        self._input = torch.empty(shape, dtype=torch.float32, device=self.device)
+
+    # ------------------------------------------------------------------ the batch kernel
+    def _groups(self):
+        return (self.batch_size * self.dataset.per_image + 3) // 4
+
+    def _make_batch(self, data, start, target, inp, seed, offset, noise=True):
+        """One svae_op_make_batch launch on the current stream: rows [start, start + B) of ``data``."""
+        lo, hi = self.dataset.range
+        p, s, g = (self.pepper_prob, self.salt_prob, self.gaussian_noise_scale) if noise else (0.0, 0.0, 0.0)
+        _lib.check(_lib.lib().svae_op_make_batch(
+            _lib.ptr(data), 1 if data.dtype == torch.uint8 else 0, None, int(start), self.batch_size,
+            self.dataset.per_image, lo, hi, p, s, g, seed, offset & 0xFFFFFFFFFFFFFFFF, _lib.ptr(target),
+            _lib.ptr(inp), _lib.stream_ptr(torch.cuda.current_stream(self.device))))
+
+    def apply_noise(self, batch):
+        """The reference's apply_noise on a given fp32 device batch [B,H,W,C], in place (the same kernel
+        with input == data); draws from the training stream.  Raises when denoise_train is off, as the
+        reference does (trainer.py:66-67)."""
+        if not self.denoise_train:
+            raise RuntimeError("Called apply_noise, but denoise_train is off")
+        if batch.dtype != torch.float32 or batch.device != self.device or not batch.is_contiguous() \
+                or list(batch.shape) != [self.batch_size] + self.data_dims:
+            raise ValueError("apply_noise takes a contiguous float32 [B,H,W,C] batch on the network's device")
+        self._make_batch(batch, 0, None, batch, self.seed, self.train_offset)
+        self.train_offset += self._groups()
+        return batch
+
+    def _next(self, test=False):
+        """The next window as (input, target) device tensors; advances the cursor and, when it corrupts,
+        the stream's offset."""
+        ds = self.dataset
+        start, _ = ds.next_test_batch(self.batch_size) if test else ds.next_batch(self.batch_size)
+        data = ds.test if test else ds.train
+        if not self.denoise_train:
+            self._make_batch(data, start, self._target, None, 0, 0, noise=False)
+            return self._target, self._target
+        if test:
+            self._make_batch(data, start, self._target, self._input, self.seed ^ self.test_seed_xor, self.test_offset)
+            self.test_offset += self._groups()
+        else:
+            self._make_batch(data, start, self._target, self._input, self.seed, self.train_offset)
+            self.train_offset += self._groups()
+        return self._input, self._target
+
+    # ------------------------------------------------------------------ the reference's loop
+    def step(self):
+        """One training iteration (trainer.py:100-104); returns network.train's loss."""
+        inp, tgt = self._next()
+        loss = self.network.train(inp, tgt)
+        self.iteration += 1
+        return loss
+
+    def train(self, num_iters=None):
+        """trainer.py:82-109: every vis_frequency iterations test + visualise, every log_loss_freq log,
+        every save_freq save a checkpoint (the reference's network saves inside its train, :254)."""
+        n = self.max_training_iters if num_iters is None else int(num_iters)
+        loss = None
+        for _ in range(n):
+            it = self.iteration
+            t0 = time.time()
+            if it % self.vis_frequency == 0:
+                err = self.test(it // self.vis_frequency)
+                self.LOG.info("Reconstruction error per pixel: %f, @ iteration: %d" % (err, it))
+                self.network.visualize(it // self.vis_frequency, self.dataset, self.base_dir)
+            loss = self.step()
+            if it % self.log_loss_freq == 0:
+                self.LOG.info("Iteration %d: Reconstruction loss %f, time per iter %fs" % (it, loss, time.time() - t0))
+            if self.base_dir is not None and self.iteration % self.save_freq == 0:
+                self.save(self.base_dir)
+        return loss
+
+    def test(self, epoch, num_iters=None):
+        """Mean over num_iters test batches of sum((recon - clean)^2) / (H W) / B (trainer.py:131), recon
+        = training_mles[-1] of forward(noisy, clean).  The engine already reduces mean((mle - target)^2)
+        per image (SVAE_BUF_REC_IMG[T-1]), so only B floats are read per batch; under
+        predict_generator_noise that buffer holds the NLL and the error is formed from x_hat."""
+        n = self.test_num_iters if num_iters is None else int(num_iters)
+        net = self.network
+        H, W, C = self.data_dims
+        T = net.cfg.mc_steps
+        err = torch.zeros((), dtype=torch.float64, device=self.device)
+        for i in range(n):
+            inp, tgt = self._next(test=True)
+            net.forward(inp, tgt, None, 1.0)
+            if net.cfg.predict_generator_noise:
+                err += (net.xhat(-1).double() - tgt.double()).square().sum() / (H * W) / self.batch_size
+            else:
+                err += net.copy_out(_lib.BUF_REC_IMG, T - 1, self.batch_size).double().mean() * C
+            if i == 0 and self.plot_reconstruction_enabled:
+                self.plot_reconstruction(epoch, tgt, inp, net.xhat(-1))
+        return float(err) / n
+
+    def plot_reconstruction(self, train_epoch, original_images, noisy_images, reconstructed_images, num_plot=3):
+        """original | noisy | reconstruction of the first num_plot images (canvas.reconstruction_canvas);
+        written to <base_dir>/reconstruction/{current, epoch<N>} and returned."""
+        disp = lambda a: self.dataset.display(a).cpu().numpy() if isinstance(a, torch.Tensor) else self.dataset.display(a)
+        c = cv.reconstruction_canvas(disp(original_images), disp(noisy_images), disp(reconstructed_images), num_plot)
+        if self.base_dir is not None:
+            folder = self.base_dir + "/reconstruction"
+            cv.save_canvas(c, folder, "current")
+            cv.save_canvas(c, folder, "epoch%d" % train_epoch)
+        return c
+
+    # ------------------------------------------------------------------ resume
+    def state_dict(self):
+        return {"iteration": self.iteration, "train_offset": self.train_offset, "test_offset": self.test_offset,
+                "seed": self.seed, "denoise_train": self.denoise_train, **self.dataset.state_dict()}
+
+    def load_state_dict(self, s):
+        self.iteration = int(s["iteration"])
+        self.train_offset, self.test_offset = int(s["train_offset"]), int(s["test_offset"])
+        self.seed = int(s.get("seed", self.seed))
+        self.dataset.load_state_dict(s)
+
+    def save(self, base_dir):
+        """The network's checkpoint and, next to it, the trainer's state as JSON."""
+        os.makedirs(base_dir, exist_ok=True)
+        self.network.save_checkpoint(os.path.join(base_dir, "model.safetensors"))
+        with open(os.path.join(base_dir, "trainer.json"), "w") as f:
+            json.dump(self.state_dict(), f)
+
+    def load(self, base_dir):
+        self.network.load_checkpoint(os.path.join(base_dir, "model.safetensors"))
+        with open(os.path.join(base_dir, "trainer.json")) as f:
+            self.load_state_dict(json.load(f))

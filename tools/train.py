@@ -1,0 +1,91 @@
+"""Train a Sequential VAE as the reference's ``main.py`` does (main.py:10-27, 49-89), on the HIP engine.
+
+    python tools/train.py --netname celeba --data faces.npy --denoise_train --plot_reconstruction
+    python tools/train.py --netname tiny --synthetic 64 --batch_size 4 --iters 100
+
+--data is an .npy file of uint8 or float images [N, H, W, C] (what a decoder of CelebA / LSUN / SVHN
+produced; the decoders themselves are not part of this project); --synthetic N makes N seeded images of
+the preset's shape.  The model directory is models/<netname>_v<version>: an existing one is refused
+without --continue_training, a missing one with it, as main.py:52-58 does.
+"""
+import argparse
+import importlib
+import logging
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+PKG = "sequential-variational-autoencoder_amd"
+
+
+def parse(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--netname", default="celeba", help="a preset of config.py (or a reference netname it maps)")
+    ap.add_argument("--batch_size", type=int, default=None, help="default: the preset's")
+    src = ap.add_mutually_exclusive_group(required=True)
+    src.add_argument("--data", help=".npy file, uint8 or float [N,H,W,C]")
+    src.add_argument("--synthetic", type=int, metavar="N", help="N seeded synthetic images")
+    ap.add_argument("--version", type=int, default=1, help="a version number for this model")
+    ap.add_argument("--continue_training", action="store_true", help="continue training an existing model")
+    ap.add_argument("--denoise_train", action="store_true", help="add salt-and-pepper and Gaussian noise to the input")
+    ap.add_argument("--plot_reconstruction", action="store_true")
+    ap.add_argument("--vis_frequency", type=int, default=1000, help="training batches per test + visualisation")
+    ap.add_argument("--iters", type=int, default=None, help="iterations to run (default: the reference's 10^7)")
+    ap.add_argument("--dtype", default="bf16x6", choices=["fp32", "bf16", "bf16x6"])
+    ap.add_argument("--models_dir", default="models")
+    ap.add_argument("--seed", type=int, default=0)
+    return ap.parse_args(argv)
+
+
+def model_dir_error(base_dir, continue_training):
+    """main.py:52-58."""
+    if not os.path.isdir(base_dir) and continue_training:
+        return "Cannot continue training a model if the file doesn't exist."
+    if os.path.isdir(base_dir) and not continue_training:
+        return "Model already exists. Either use a new version number, or, set the --continue_training flag"
+    return None
+
+
+def main(argv=None):
+    a = parse(argv)
+    base_dir = os.path.join(a.models_dir, "%s_v%d" % (a.netname, a.version))
+    err = model_dir_error(base_dir, a.continue_training)
+    if err:
+        print(err)
+        return 1
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        print("tools/train.py needs a GPU (the engine has no CPU path)")
+        return 1
+    cfgmod = importlib.import_module(PKG + ".config")
+    SV = importlib.import_module(PKG + ".sequential_vae").SequentialVAE
+    DS = importlib.import_module(PKG + ".data").DeviceDataset
+    NT = importlib.import_module(PKG + ".trainer").NoisyTrainer
+    over = dict(dtype=a.dtype)
+    if a.batch_size:
+        over["batch"] = a.batch_size
+    cfg = cfgmod.preset(a.netname, **over)
+    if a.data:
+        ds = DS.from_array(np.load(a.data), range=cfg.range, name=os.path.basename(a.data), device="cuda")
+    else:
+        ds = DS.synthetic(a.synthetic, cfg.height, cfg.width, cfg.channels, seed=a.seed, range=cfg.range, device="cuda")
+    os.makedirs(base_dir, exist_ok=True)
+    logging.basicConfig(filename=os.path.join(base_dir, "log"), level=logging.INFO)
+    log = logging.getLogger(a.netname)
+    net = SV(cfg, seed=a.seed)
+    net.name = a.netname
+    trainer = NT(net, ds, denoise_train=a.denoise_train, vis_frequency=a.vis_frequency,
+                 plot_reconstruction=a.plot_reconstruction, base_dir=base_dir, logger=log, seed=a.seed)
+    if a.continue_training and os.path.exists(os.path.join(base_dir, "trainer.json")):
+        trainer.load(base_dir)
+        log.info("resumed at iteration %d" % trainer.iteration)
+    loss = trainer.train(a.iters)
+    trainer.save(base_dir)
+    print("iteration %d: reconstruction loss %s" % (trainer.iteration, loss))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
