@@ -30,19 +30,11 @@ __device__ __forceinline__ f32x4 bn_y(f32x4 x, f32x4 m, f32x4 is, f32x4 b) {
 // a separate finalize launch per BN layer.
 #define AP_QB 64
 
-// SVAE_BN_W8=1: bf16-output BN passes with 8 channels per thread (one 16-byte store)
-static bool bn_w8() {
-  static const bool v = svae_knob("SVAE_BN_W8", 0) == 1;
-  return v;
-}
-
 // shards so that at most ~16 row-blocks add into one accumulator line
 // cap: 16 (bf16 mode) or 32 (split mode: +0.8 % there, -1 % in bf16; profiles/r04_shards_ab.txt); the
-// apply blocks each gather nsh x 4 words per channel, the producers' atomics contend with fewer (SVAE_BN_SHMAX
-// overrides: 8 -3 %, 4 -13 %)
+// apply blocks each gather nsh x 4 words per channel, the producers' atomics contend with fewer (a cap of
+// 8: -3 %, 4: -13 %)
 int bn_acc_shards(long long rowblocks, int cap) {
-  static const int over = svae_knob("SVAE_BN_SHMAX", 0);
-  if (over > 0) cap = over;
   int n = 1;
   while (n < cap && (long long)n * 16 < rowblocks) n *= 2;
   return n;
@@ -85,7 +77,7 @@ struct ApGrid {
   dim3 grid;
   int rpb;
 };
-// W = channels per thread: 4 (one 16-byte fp32 quad), or 8 for bf16 outputs (one 16-byte bf16 store)
+// W = channels per thread: 4 (one 16-byte fp32 quad)
 static ApGrid ap_grid(long long rows, int C, int groups, int W = 4) {
   const int Q = C / W;
   const int QB = Q < AP_QB * 4 / W ? Q : AP_QB * 4 / W;
@@ -108,8 +100,6 @@ static ApGrid ap_grid(long long rows, int C, int groups, int W = 4) {
   return g;
 }
 
-// W = 8 (bf16 output, C % 8 == 0): each thread normalises 8 consecutive channels of a row and
-// writes them as one 16-byte bf16 vector (write-through-friendly; W = 4 writes 8 bytes)
 // PB: pre is stored as bf16 (common.h pf_ld4)
 template <int W, bool PB>
 __global__ __launch_bounds__(256) void bn_apply_kernel(const float* pre, int ldp, long long pre_gs, long long rows,
@@ -162,32 +152,6 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* pre, int ldp
   if (res) res += group * res_gs;
   const long long r0 = (long long)blockIdx.y * rpb;
   const long long r1 = r0 + rpb < rows ? r0 + rpb : rows;
-  if constexpr (W == 8) {  // (out_bf16)
-    const f32x4 m0 = *(const f32x4*)&sm[0][qi * 8], is0 = *(const f32x4*)&sm[1][qi * 8];
-    const f32x4 m1 = *(const f32x4*)&sm[0][qi * 8 + 4], is1 = *(const f32x4*)&sm[1][qi * 8 + 4];
-    const f32x4 b0 = *(const f32x4*)(beta + group * beta_gs + c), b1 = *(const f32x4*)(beta + group * beta_gs + c + 4);
-#pragma unroll 4
-    for (long long r = r0 + rl; r < r1; r += RL) {
-      f32x4 y0 = bn_y(pf_ld4(pre, r * ldp + c, PB), m0, is0, b0);
-      f32x4 y1 = bn_y(pf_ld4(pre, r * ldp + c + 4, PB), m1, is1, b1);
-      if (res) {
-        y0 += *(const f32x4*)(res + r * ldr + c);
-        y1 += *(const f32x4*)(res + r * ldr + c + 4);
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        y0[e] = act_f(y0[e], act);
-        y1[e] = act_f(y1[e], act);
-      }
-      const long long o = group * out_gs + r * ldo + c;  // bf16 elements (a multiple of 8)
-      const bf16x4_bn h0 = __builtin_convertvector(y0, bf16x4_bn), h1 = __builtin_convertvector(y1, bf16x4_bn);
-      const u64 u0 = __builtin_bit_cast(u64, h0), u1 = __builtin_bit_cast(u64, h1);
-      const f32x4 bits = {__uint_as_float((unsigned)u0), __uint_as_float((unsigned)(u0 >> 32)),
-                          __uint_as_float((unsigned)u1), __uint_as_float((unsigned)(u1 >> 32))};
-      st_out16(out, o / 2, bits);
-    }
-    return;
-  }
   const f32x4 m = *(const f32x4*)&sm[0][qi * 4], is = *(const f32x4*)&sm[1][qi * 4];
   const f32x4 b = *(const f32x4*)(beta + group * beta_gs + c);
 #pragma unroll 4
@@ -208,16 +172,6 @@ void bn_apply(const float* pre, int ldp, long long pre_gs, long long rows, int C
               long long sh, int nsh, float eps, float* mean, float* invstd, long long ms_gs, const float* beta, long long beta_gs,
               const float* res, int ldr, long long res_gs, int act, float* out, int ldo, long long out_gs, int groups,
               hipStream_t s, int out_bf16, int pre_bf16) {
-  if (out_bf16 && bn_w8() && C % 8 == 0 && ldo % 8 == 0 && out_gs % 8 == 0 && ((uintptr_t)out & 15) == 0) {
-    const ApGrid g = ap_grid(rows, C, groups, 8);
-    if (pre_bf16)
-      hipLaunchKernelGGL((bn_apply_kernel<8, true>), g.grid, dim3(256), 0, s, pre, ldp, pre_gs, rows, C, acc, acc_gs, sh, nsh,
-                         eps, mean, invstd, ms_gs, beta, beta_gs, res, ldr, res_gs, act, out, ldo, out_gs, g.rpb, out_bf16);
-    else
-      hipLaunchKernelGGL((bn_apply_kernel<8, false>), g.grid, dim3(256), 0, s, pre, ldp, pre_gs, rows, C, acc, acc_gs, sh, nsh,
-                         eps, mean, invstd, ms_gs, beta, beta_gs, res, ldr, res_gs, act, out, ldo, out_gs, g.rpb, out_bf16);
-    return;
-  }
   const ApGrid g = ap_grid(rows, C, groups);
   if (pre_bf16)
     hipLaunchKernelGGL((bn_apply_kernel<4, true>), g.grid, dim3(256), 0, s, pre, ldp, pre_gs, rows, C, acc, acc_gs, sh, nsh,
@@ -343,7 +297,6 @@ void bn_bwd_reduce(const float* dy, int lddy, long long dy_gs, const float* y, i
 #undef BWR_LAUNCH
 }
 
-// W = 8 (bf16 dpre, C % 8 == 0): 8 channels per thread, one 16-byte bf16 store per row
 template <int W, bool PB, bool YB>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
     const float* dy, int lddy, long long dy_gs, const float* y, int ldy, long long y_gs, const float* pre, int ldp,
@@ -387,43 +340,6 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
   if (y) y = pf_at(y, group * y_gs, YB);
   pre = pf_at(pre, group * pre_gs, PB);
   if (dres) dres += group * dres_gs;
-  if constexpr (W == 8) {  // (dpre_bf16)
-    const long long r0 = (long long)blockIdx.y * rpb;
-    const long long r1 = r0 + rpb < rows ? r0 + rpb : rows;
-    f32x4 mm[2], iss[2], bbb[2], aa[2], bq[2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      mm[h] = *(const f32x4*)(mean + group * ms_gs + c + 4 * h);
-      iss[h] = *(const f32x4*)(invstd + group * ms_gs + c + 4 * h);
-      bbb[h] = y ? f32x4{0.f, 0.f, 0.f, 0.f} : *(const f32x4*)(beta + group * beta_gs + c + 4 * h);
-      aa[h] = *(const f32x4*)&sm[0][qi * 8 + 4 * h];
-      bq[h] = *(const f32x4*)&sm[1][qi * 8 + 4 * h];
-    }
-#pragma unroll 2
-    for (long long r = r0 + rl; r < r1; r += RL) {
-      u64 u[2];
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const f32x4 g = *(const f32x4*)(dy + r * lddy + c + 4 * h);
-        const f32x4 xp = pf_ld4(pre, r * ldp + c + 4 * h, PB);
-        const f32x4 yy = y ? pf_ld4(y, r * ldy + c + 4 * h, YB) : bn_y(xp, mm[h], iss[h], bbb[h]);
-        const f32x4 xh = (xp - mm[h]) * iss[h];
-        f32x4 dz;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) dz[e] = g[e] * dact_from_y(yy[e], act);
-        const f32x4 dp = iss[h] * (dz - aa[h] - xh * bq[h]);
-        u[h] = __builtin_bit_cast(u64, __builtin_convertvector(dp, bf16x4_bn));
-        if (dres) {
-          f32x4* d = (f32x4*)(dres + r * ldres + c + 4 * h);
-          *d = res_acc ? *d + dz : dz;
-        }
-      }
-      const f32x4 bits = {__uint_as_float((unsigned)u[0]), __uint_as_float((unsigned)(u[0] >> 32)),
-                          __uint_as_float((unsigned)u[1]), __uint_as_float((unsigned)(u[1] >> 32))};
-      st_out16(dpre, (group * dpre_gs + r * lddp + c) / 2, bits);
-    }
-    return;
-  }
   const f32x4 m = *(const f32x4*)(mean + group * ms_gs + c), is = *(const f32x4*)(invstd + group * ms_gs + c);
   const f32x4 bb = y ? f32x4{0.f, 0.f, 0.f, 0.f} : *(const f32x4*)(beta + group * beta_gs + c);
   const f32x4 a = *(const f32x4*)&sm[0][qi * 4], b = *(const f32x4*)&sm[1][qi * 4];
@@ -469,11 +385,6 @@ void bn_bwd_apply(const float* dy, int lddy, long long dy_gs, const float* y, in
   } else {                                                                                                         \
     if (yb) BWA_ONE(W_, false, true, G_);                                                                          \
     else BWA_ONE(W_, false, false, G_);                                                                            \
-  }
-  if (dpre_bf16 && bn_w8() && C % 8 == 0 && lddp % 8 == 0 && dpre_gs % 8 == 0 && ((uintptr_t)dpre & 15) == 0) {
-    const ApGrid g = ap_grid(rows, C, groups, 8);
-    BWA_LAUNCH(8, g)
-    return;
   }
   const ApGrid g = ap_grid(rows, C, groups);
   BWA_LAUNCH(4, g)

@@ -220,7 +220,7 @@ __device__ __forceinline__ void stat_put(u64* acc, int c, float s, float q) {
 // integers and writes mean / invstd with bn_apply's own fp64 expression (bitwise what bn_apply would
 // compute), so the apply pass reads two floats per channel instead of gathering nsh x 4 words per channel
 // in every block (that gather, served from the memory side since the atomics bypass the XCD L2s, cost
-// 2.5 % of the bf16 step and 7 % of the bf16x6 step: SVAE_DBG_SKIP=16 probe)
+// 2.5 % of the bf16 step and 7 % of the bf16x6 step, by a timing probe)
 struct BnFin {
   u64* cnt;            // arrival counters [group] (zeroed with the accumulators once per pass); nullptr: off
   int nblk;            // producer blocks (tiles) per group: set by the launcher

@@ -529,15 +529,6 @@ struct svae_ctx {
   static constexpr int NR = 6;  // "ready" events (re-recorded in turn: each is waited on right after its record)
   bool side = false;
   hipStream_t st2 = nullptr;
-  // SVAE_SIDE2=1: a second weight-gradient stream; the conv weight-GEMMs alternate between st2 and st2b
-  // (own split slab each).  A wgrad launch holds ~64 CUs, so two run side by side where one left
-  // the rest of the machine to latency-bound main-stream kernels.  Every ordering point that
-  // follows "the side stream" first merges st2b into st2 (side_merge).
-  hipStream_t st2b = nullptr;
-  float* slab2b = nullptr;
-  hipEvent_t ev_merge = nullptr;
-  unsigned side_rr = 0;
-  bool side_pin = false;  // the closure being handed over uses shared scratch: st2 only
   hipStream_t st3 = nullptr;  // split-latent FCs (fwd up front, bwd per level): no weight-GEMM queue ahead
   hipEvent_t ev_dz = nullptr, ev_j3 = nullptr;
   // recognition backward overlapped with the chain backward: groups of rec_group steps on st4 as soon
@@ -546,10 +537,6 @@ struct svae_ctx {
   hipEvent_t ev_j4 = nullptr;
   float* slab4 = nullptr;
   int rec_group = 0;
-  // forward recognition split (SVAE_REC_SPLIT=1): step 0's ladder on the main stream, the batched
-  // ladders of steps 1..T-1 on st4 (own split slab), overlapping the chain's step 0
-  int rec_split = 0;
-  hipEvent_t ev_rs = nullptr, ev_rs2 = nullptr;
   float* slab2 = nullptr;
   // BN-backward outputs read by the side stream's weight GEMMs: every one of a backward pass gets
   // its own region of these arenas (bump-allocated, reset per pass), so the main stream never
@@ -569,7 +556,6 @@ struct svae_ctx {
   // marker packet that drains the queue before the next dispatch (a 4-10 us gap per record).
   std::vector<std::function<int()>> side_q;
   int side_batch = 1;
-  bool side2 = false;  // SVAE_SIDE2 (read at svae_create, before the arena plan)
   bool fc_fuse = true;  // E.fc BN-backward sums fused into the top FC's input gradient (SVAE_BWFUSE_FC)
   // SVAE_FOLD=1: the forward BN apply of a layer whose only main-stream consumer is a wave-split halo
   // gather runs on st2 (for the backward's weight gradients), and the gather stages act(bn_y(pre))
@@ -882,18 +868,11 @@ struct Slot {
 // size) the main stream waits for the side stream to drain and the arena starts over
 static int side_flush(svae_ctx* c, hipStream_t also = nullptr);
 static int side_run_queued(svae_ctx* c);
-// st2 after everything enqueued so far on st2b (no-op without the second side stream)
-static void side_merge(svae_ctx* c) {
-  if (!c->st2b) return;
-  hipEventRecord(c->ev_merge, c->st2b);
-  hipStreamWaitEvent(c->st2, c->ev_merge, 0);
-}
 static float* arena_next(svae_ctx* c, float* base, long long cap, long long& off, long long n,
                          bool st3_reads = false) {
   n = (n + 63) / 64 * 64;
   if (off + n > cap) {
     side_flush(c);
-    if (!st3_reads) side_merge(c);
     hipEvent_t ev = st3_reads ? c->ev_drain3 : c->ev_drain;
     hipEventRecord(ev, st3_reads ? c->st3 : c->st2);
     hipStreamWaitEvent(c->st, ev, 0);
@@ -960,14 +939,12 @@ template <class Fn>
 static int on_side_q(svae_ctx* c, hipEvent_t ready, Fn&& fn) {
   if (!c->side || !ready || c->side_batch <= 1) {
     if (c->side && ready) {
-      const bool b = c->st2b && !c->side_pin && (c->side_rr++ & 1);
-      hipStream_t sx = b ? c->st2b : c->st2;
       hipEventRecord(ready, c->st);
-      hipStreamWaitEvent(sx, ready, 0);
+      hipStreamWaitEvent(c->st2, ready, 0);
       hipStream_t s0 = c->st;
       float* sl0 = c->slab;
-      c->st = sx;
-      c->slab = b ? c->slab2b : c->slab2;
+      c->st = c->st2;
+      c->slab = c->slab2;
       const int r = fn();
       c->st = s0;
       c->slab = sl0;
@@ -1112,25 +1089,6 @@ static void wgemm(svae_ctx* c, const WgArgs& w, int groups) {
   wgrad_bf16(w, groups, c->st);
 }
 
-// SVAE_DBG_SKIP (timing probe, WRONG RESULTS): bit 0 skips the forward BN apply of the layers whose
-// output only bf16 GEMMs read, bit 1 the backward BN apply of the conv layers without a shortcut --
-// the step time without the passes a consumer-side fold would remove (an upper bound of its gain);
-// bit 2 every conv weight gradient (side stream), bit 3 the per-bucket Adam of the chain steps; bit 4 makes
-// the conv layers' forward BN apply read last step's mean / invstd instead of finalising the statistics
-// accumulators per block (the gain a producer-side finalise could bring).  Compiled only into a
-// -DSVAE_DEBUG_PROBES build: the shipping library ignores the variable (tests/test_knobs.py)
-#ifdef SVAE_DEBUG_PROBES
-static int dbg_skip() {
-  static const int v = [] {
-    const char* e = getenv("SVAE_DBG_SKIP");
-    return e ? atoi(e) : 0;
-  }();
-  return v;
-}
-#else
-static inline int dbg_skip() { return 0; }
-#endif
-
 // the consumer-side BN gather is available for this launch (the wave-split halo gather takes it)
 static bool ain_ok(svae_ctx* c, const FwdArgs& t, int groups) {
   // (the split mode's gathers scale their staged window by its running maximum, taken before a
@@ -1194,7 +1152,6 @@ static int conv_bn_act_fwd(svae_ctx* c, const ConvL& L, int groups, long long w_
     }
   }
   gemm(c, a, groups);
-  if ((dbg_skip() & 1) && out.bf && !res.p) return 0;  // TIMING PROBE ONLY (wrong results): no apply pass
   if (dfr_out && c->fold && c->side && !res.p) {  // the apply on st2, off the critical path
     hipEvent_t ready = c->ev_fold[c->fold_pos];
     hipEvent_t applied = c->ev_fold[c->fold_pos + 1];
@@ -1221,12 +1178,12 @@ static int conv_bn_act_fwd(svae_ctx* c, const ConvL& L, int groups, long long w_
     return 0;
   }
   if (dfr_out) *dfr_out = Defer{};
-  if (c->bnfin && !fin && !(dbg_skip() & 16)) {  // the statistics finalised once, read by every apply block
+  if (c->bnfin && !fin) {  // the statistics finalised once, read by every apply block
     bn_finalize(acc.p, acc.gs, acc.sh, acc.nsh, rows, L.cout, 1e-3f, bn.mean, bn.invstd, bn_gs, nullptr, nullptr, 0,
                 groups, c->st);
     fin = true;
   }
-  bn_apply(pre, L.cout, pre_gs, rows, L.cout, (fin || (dbg_skip() & 16)) ? nullptr : acc.p, acc.gs, acc.sh, acc.nsh, 1e-3f, bn.mean,
+  bn_apply(pre, L.cout, pre_gs, rows, L.cout, fin ? nullptr : acc.p, acc.gs, acc.sh, acc.nsh, 1e-3f, bn.mean,
            bn.invstd, bn_gs, c->P + L.obeta, w_gs, res.p, res.ld, res.gs, act, out.p, out.ld, out.gs, groups, c->st, out.bf,
            c->pbf);
   return 0;
@@ -1257,7 +1214,6 @@ static int dpre_bf(const svae_ctx* c, const ConvL& L) {
 static int conv_wgrad(svae_ctx* c, const ConvL& L, int groups, long long w_gs, View in, const float* dpre,
                       long long dpre_gs, float* dW) {
   const int B = c->m.g.B;
-  if (dbg_skip() & 4) return 0;  // TIMING PROBE ONLY (wrong results): no conv weight gradients
   WgArgs w{};
   w.g.ksz = 4;
   w.g.pad = 1;
@@ -1478,7 +1434,6 @@ static int bn_act_bwd(svae_ctx* c, int groups, long long rows, int C, View dy, V
   if (!pre_reduced)
     bn_bwd_reduce(dy.p, dy.ld, dy.gs, yp, y.ld, y.gs, pre, ldp, pre_gs, rows, C, bn.mean, bn.invstd, bn_gs, beta, w_gs,
                   act, acc.p, acc.gs, acc.sh, acc.nsh, groups, c->st, pre_bf16, yp ? y.bf : 0);
-  if ((dbg_skip() & 2) && !dres.p && rows > c->m.g.B) return 0;  // TIMING PROBE ONLY (wrong results)
   const float* ab = pre_reduced ? fu->ab : nullptr;
   if (c->bnfin && !ab) {  // a, b and dbeta finalised once, read by every apply block
     float* t = (float*)acc_take(c, (long long)groups * C);  // [group][2C] floats
@@ -1588,14 +1543,13 @@ static int step_hook(svae_ctx* c, int t) {
     hipEventRecord(ev, c->st);
     hipStreamWaitEvent(c->st2, ev, 0);
     if (int r = side_run_queued(c)) return r;  // the step's queued weight gradients, before its bucket
-    side_merge(c);
     hipEventRecord(c->ev_j3, c->st3);  // the step's split-latent gradients
     hipStreamWaitEvent(c->st2, c->ev_j3, 0);
   }
   if (c->hook) c->hook(c->hook_user, t);
   // the bucket's update follows whatever exchange the hook ordered on the side stream; the
   // backward of steps < t reads neither theta_t nor its shadows
-  if (c->fa_on && !(dbg_skip() & 8)) adam_range(c, c->m.step_lo[t], c->m.step_hi[t], c->fa_lr, c->fa_step, c->fa_clip, c->st2);
+  if (c->fa_on) adam_range(c, c->m.step_lo[t], c->m.step_hi[t], c->fa_lr, c->fa_step, c->fa_clip, c->st2);
   return 0;
 }
 
@@ -1660,13 +1614,7 @@ static int inference_fwd(svae_ctx* c, int t0, int n, View in0) {
 // split_latent of step t (:1796-1806): ladder_i straight into the step's concat buffers
 // The output / ratio conv-T operands of every step, PACK_MAXT steps per launch (misc.hip
 // pack_out_kernel): [tap][C+1][F1] weights (ratio row zero at t = 0), 4 bias floats, bf16 copy.
-static bool pack_step_mode() {
-  static const bool v = svae_knob("SVAE_PACK_STEP", 0) == 1;
-  return v;
-}
-
 static void pack_out_all(svae_ctx* c, hipStream_t st) {
-  if (pack_step_mode()) return;
   const Model& M = c->m;
   const Geo& g = M.g;
   for (int t0 = 0; t0 < g.Te; t0 += PACK_MAXT) {
@@ -1978,24 +1926,8 @@ static int engine_forward(svae_ctx* c) {
   c->eps_used = eps;
   // recognition: q(z_t | x) for every step at once (groups = T), or, in Latent InfoMax mode,
   // q(z_0 | x) here and q(z_t | x_{t-1}) inside the chain (create_recognition_network :1013-1027)
-  if (c->rec_split && c->st4 && !g.plc && T > 1) {
-    if ((r = inference_fwd(c, 0, 1, View{(float*)c->x_in, g.C, 0}))) return r;
-    hipEventRecord(c->ev_rs, st);
-    hipStreamWaitEvent(c->st4, c->ev_rs, 0);
-    hipStream_t s0 = c->st;
-    float* sl0 = c->slab;
-    c->st = c->st4;
-    c->slab = c->slab4;
-    r = inference_fwd(c, 1, T - 1, View{(float*)c->x_in, g.C, 0});
-    c->st = s0;
-    c->slab = sl0;
-    if (r) return r;
-    hipEventRecord(c->ev_rs2, c->st4);
-  } else if ((r = inference_fwd(c, 0, g.plc ? 1 : T, View{(float*)c->x_in, g.C, 0}))) {
-    return r;
-  }
+  if ((r = inference_fwd(c, 0, g.plc ? 1 : T, View{(float*)c->x_in, g.C, 0}))) return r;
   }  // !generative
-  const bool rsplit = c->rec_split && c->st4 && !g.plc && T > 1 && !c->generative;
   // split_latent of every step on the side stream (z is known for all steps unless Latent
   // InfoMax draws z_t inside the chain); step t's decoder waits on ev_sfc[t]
   static const int sfc_mode = svae_knob("SVAE_SFC", 1);  // 0 = split-latent forward on the main stream per step
@@ -2005,9 +1937,9 @@ static int engine_forward(svae_ctx* c) {
   static const bool pack_first = svae_knob("SVAE_PACK_FIRST", 1) != 0;
   if (pack_first) pack_out_all(c, st);
   // every step's split-latent forward batched per level (SVAE_SFC_STEPS=0: one launch per level and step, the
-  // round-5 schedule); not with the knob-only recognition split, whose z_t of steps >= 1 arrive later
+  // round-5 schedule)
   static const bool sfc_steps = svae_knob("SVAE_SFC_STEPS", 1) != 0;
-  const bool sfc_all = sfc_side && sfc_steps && !rsplit;
+  const bool sfc_all = sfc_side && sfc_steps;
   if (sfc_side) {
     hipEventRecord(c->ev_aux, st);
     hipStreamWaitEvent(c->st3, c->ev_aux, 0);
@@ -2015,7 +1947,6 @@ static int engine_forward(svae_ctx* c) {
       split_latent_fwd_all(c, c->st3, c->ev_sfc[0], c->ev_sfc[1]);
     } else {
       for (int t = 0; t < g.Te; ++t) {
-        if (t == 1 && rsplit) hipStreamWaitEvent(c->st3, c->ev_rs2, 0);  // z_t of steps >= 1 (st4)
         split_latent_fwd(c, t, c->st3);
         hipEventRecord(c->ev_sfc[t], c->st3);
       }
@@ -2027,7 +1958,6 @@ static int engine_forward(svae_ctx* c) {
   // ---------------- the chain ----------------
   for (int t = 0; t < T; ++t) {
     svae_ctx::StepBufs& s = c->sb[t];
-    if (t == 1 && rsplit) hipStreamWaitEvent(st, c->ev_rs2, 0);  // recognition of steps >= 1 (st4)
     if (g.flat && t >= 1) {  // flat generator step: no encoder, split-latent or ladder
       if ((r = flat_forward(c, t))) return r;
       continue;
@@ -2093,24 +2023,8 @@ static int engine_forward(svae_ctx* c) {
       const int C1 = g.C + 1;
       const int F1 = F[1];
       // pack [tap][C+1][F1] (ratio row zero at t=0) for the fused output conv-T and its dgrad
-      // (wpack / wpack_h / bias packed for every step by pack_out_all at the start of the forward;
-      // SVAE_PACK_STEP=1: the former per-step copies, kept for bitwise A/B checks)
+      // (wpack / wpack_h / bias packed for every step by pack_out_all at the start of the forward)
       float* bpack = s.wpack + 16 * C1 * F1;
-      if (pack_step_mode()) {
-        HIPCHK(c, hipMemsetAsync(s.wpack, 0, (size_t)(16 * C1 * F1 + 4) * sizeof(float), st));
-        HIPCHK(c, hipMemcpyAsync(bpack, c->P + G.obout, g.C * sizeof(float), hipMemcpyDeviceToDevice, st));
-        if (t >= 1) HIPCHK(c, hipMemcpyAsync(bpack + g.C, c->P + G.obratio, sizeof(float), hipMemcpyDeviceToDevice, st));
-        HIPCHK(c, hipMemcpy2DAsync(s.wpack, (size_t)C1 * F1 * sizeof(float), c->P + G.owout,
-                                   (size_t)g.C * F1 * sizeof(float), (size_t)g.C * F1 * sizeof(float), 16,
-                                   hipMemcpyDeviceToDevice, st));
-        if (t >= 1)
-          HIPCHK(c, hipMemcpy2DAsync(s.wpack + g.C * F1, (size_t)C1 * F1 * sizeof(float), c->P + G.owratio,
-                                     (size_t)F1 * sizeof(float), (size_t)F1 * sizeof(float), 16,
-                                     hipMemcpyDeviceToDevice, st));
-        if (g.bf16)
-          shadow_weights(s.wpack, s.wpack_h, nullptr, 16LL * C1 * F1, nullptr, 0, nullptr, g.split ? 3 : 1,
-                         g.split ? 16LL * C1 * F1 : 0, st);
-      }
       ConvGeom og{GM_CONVT, B, S[1], S[1], g.H, g.W, 2, 1, 4};
       if (g.bf16) {  // small-N conv-T gather (split mode: on the three planes of the packed weights), bias in the epilogue
         FwdArgs a{};
@@ -2280,7 +2194,6 @@ static int engine_backward_pass(svae_ctx* c) {
   if (c->side) {  // the side stream starts after the forward (and anything before it)
     hipEventRecord(c->ev_start, st);
     hipStreamWaitEvent(c->st2, c->ev_start, 0);
-    if (c->st2b) hipStreamWaitEvent(c->st2b, c->ev_start, 0);
     // re-arm the slot-free events on the main stream: the previous backward's side-stream work
     // was joined into it, so "free" holds now, and every later wait depends only on work of this
     // pass (required when the step is captured into a graph)
@@ -2366,7 +2279,6 @@ static int engine_backward_pass(svae_ctx* c) {
       float* gratio = t >= 1 ? c->Gr + G.owratio : nullptr;
       float* gbout = c->Gr + G.obout;
       float* gbratio = t >= 1 ? c->Gr + G.obratio : nullptr;
-      c->side_pin = true;  // (colsum_small's cs_part scratch is shared by every step's closure)
       if ((r = on_side_q(c, c->ev_da_ready, [=]() mutable {
         w.part = c->slab;
         const int ns = (bfk || g.split) ? wgrad_smallc_part(w, 1, c->slab, c->slab_cap, c->st) : 0;
@@ -2377,7 +2289,6 @@ static int engine_backward_pass(svae_ctx* c) {
         colsum_small(da, C1, P0, M_out, c->cs_part, gbout, Cc, gbratio, c->st);
         return 0;
       }))) return r;
-      c->side_pin = false;
       // d cur = conv-T dgrad (CONV gather over da with the packed [tap][C+1][F1] weights as KN)
       FwdArgs a{};
       a.A = c->da; a.lda = C1;
@@ -2605,8 +2516,7 @@ static int engine_backward_pass(svae_ctx* c) {
   if ((r = side_flush(c))) return r;
   if (M.shared) {  // public gradient = fixed-order sum of the step copies (side stream joined first)
     if (c->side) {
-      side_merge(c);
-    hipEventRecord(c->ev_join, c->st2);
+      hipEventRecord(c->ev_join, c->st2);
       hipStreamWaitEvent(st, c->ev_join, 0);
       hipEventRecord(c->ev_j3, c->st3);
       hipStreamWaitEvent(st, c->ev_j3, 0);
@@ -2807,8 +2717,7 @@ static bool plan(svae_ctx* c) {
   c->slab_cap = 64LL << 20;
   c->slab = A(c->slab_cap);
   c->slab2 = A(c->slab_cap);
-  if (c->side2) c->slab2b = A(c->slab_cap);
-  if (c->rec_group > 0 || c->rec_split) c->slab4 = A(c->slab_cap);
+  if (c->rec_group > 0) c->slab4 = A(c->slab_cap);
   c->cs_part = A(64 * 1024);
   c->zero_img = A((long long)B * g.H * g.W * g.C);
   return true;
@@ -2876,10 +2785,8 @@ int svae_create(const svae_config* cfg, int device, svae_ctx** out) {
   {
     // measured-slower alternatives, reachable only in a -DSVAE_KNOBS build, read per context
     c->fold = svae_knob("SVAE_FOLD", 0) == 1;          // forward BN applies of gather-only tensors on st2
-    c->side2 = svae_knob("SVAE_SIDE2", 0) == 1;        // a second weight-gradient stream
     c->rec_group = svae_knob("SVAE_REC_GROUP", 0);     // recognition-backward group size (0 = batched after the chain)
     if (c->rec_group < 0 || c->m.g.plc) c->rec_group = 0;
-    c->rec_split = (svae_knob("SVAE_REC_SPLIT", 0) == 1 && !c->m.g.plc && c->m.g.T > 1) ? 1 : 0;  // forward recognition of steps >= 1 on st4
   }
   {
     // operand storage in bf16 mode; the fp32 alternatives are bitwise A/B checks (knob builds)
@@ -3037,32 +2944,14 @@ int svae_create(const svae_config* cfg, int device, svae_ctx** out) {
   hipHostMalloc((void**)&c->reg_host, 64 * sizeof(float), hipHostMallocDefault);
   {
     if (svae_knob("SVAE_NO_SIDE", 0) != 1) {
-      // SVAE_SIDE_CUMASK=k (A/B): the weight-gradient stream runs on all CUs but every k-th, so the
-      // main stream's latency-bound kernels always find free CUs.  A CU-masked stream is a blocking
-      // stream (it synchronises with the NULL stream), so this is only meaningful when the caller's
-      // stream is not the NULL stream (bench.py SVAE_BENCH_STREAM=1)
-      const int cmk = svae_knob("SVAE_SIDE_CUMASK", 0);
-      bool ok;
-      if (cmk >= 2) {
-        int ncu = 0;
-        hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device);
-        std::vector<uint32_t> mask((ncu + 31) / 32, 0u);
-        for (int i = 0; i < ncu; ++i)
-          if (i % cmk != cmk - 1) mask[i / 32] |= 1u << (i % 32);
-        ok = hipExtStreamCreateWithCUMask(&c->st2, (uint32_t)mask.size(), mask.data()) == hipSuccess;
-      } else {
-        ok = hipStreamCreateWithFlags(&c->st2, hipStreamNonBlocking) == hipSuccess;
-      }
+      bool ok = hipStreamCreateWithFlags(&c->st2, hipStreamNonBlocking) == hipSuccess;
       ok = ok && hipStreamCreateWithFlags(&c->st3, hipStreamNonBlocking) == hipSuccess;
-      if (c->side2) ok = ok && hipStreamCreateWithFlags(&c->st2b, hipStreamNonBlocking) == hipSuccess;
-      if (c->rec_group > 0 || c->rec_split)
+      if (c->rec_group > 0)
         ok = ok && hipStreamCreateWithFlags(&c->st4, hipStreamNonBlocking) == hipSuccess;
       // cross-stream ordering on this device only: no system-scope fence (a system-scope release
       // writes the L2s back for host / peer visibility, a GPU-side bubble at every record); the
       // gradient-hook event, which orders a collective's peer traffic, keeps it
-      // (SVAE_EV_SYSFENCE=1: every event with the system fence)
-      static const bool sysf = svae_knob("SVAE_EV_SYSFENCE", 0) == 1;
-      const unsigned evf = hipEventDisableTiming | (sysf ? 0u : (unsigned)hipEventDisableSystemFence);
+      const unsigned evf = hipEventDisableTiming | hipEventDisableSystemFence;
       auto mk = [&](hipEvent_t* ev) { ok = ok && hipEventCreateWithFlags(ev, evf) == hipSuccess; };
       for (int i = 0; i < svae_ctx::NR; ++i) { mk(&c->ev_ready[i]); mk(&c->ev_iready[i]); }
       mk(&c->ev_drain);
@@ -3073,9 +2962,6 @@ int svae_create(const svae_config* cfg, int device, svae_ctx** out) {
       mk(&c->ev_drain3);
       for (int i = 0; i < 64; ++i) mk(&c->ev_sfc[i]);
       for (int i = 0; i < svae_ctx::NF; ++i) mk(&c->ev_flush[i]);
-      mk(&c->ev_rs);
-      mk(&c->ev_rs2);
-      if (c->side2) mk(&c->ev_merge);
       for (int i = 0; i < svae_ctx::NFOLD; ++i) mk(&c->ev_fold[i]);
       mk(&c->ev_fold_join);
       {  // SVAE_SIDE_BATCH (read per context): weight-gradient layers per side-stream hand-over
@@ -3094,7 +2980,7 @@ int svae_create(const svae_config* cfg, int device, svae_ctx** out) {
 
 int svae_destroy(svae_ctx* c) {
   if (!c) return 0;
-  for (hipStream_t sx : {c->st2b, c->st2, c->st3, c->st4})
+  for (hipStream_t sx : {c->st2, c->st3, c->st4})
     if (sx) {
       hipStreamSynchronize(sx);
       hipStreamDestroy(sx);
@@ -3106,7 +2992,7 @@ int svae_destroy(svae_ctx* c) {
     if (ev) hipEventDestroy(ev);
   for (hipEvent_t ev : c->ev_flush)
     if (ev) hipEventDestroy(ev);
-  for (hipEvent_t ev : {c->ev_rs, c->ev_rs2, c->ev_merge, c->ev_fold_join})
+  for (hipEvent_t ev : {c->ev_fold_join})
     if (ev) hipEventDestroy(ev);
   for (hipEvent_t ev : c->ev_fold)
     if (ev) hipEventDestroy(ev);
@@ -3245,7 +3131,6 @@ int svae_backward(svae_ctx* c, void* stream) {
   int r = engine_backward(c);
   c->ext_dx = c->ext_dz = nullptr;  // one-shot
   if (c->side) {  // join: the side stream's weight gradients are ordered before later caller work
-    side_merge(c);
     hipEventRecord(c->ev_join, c->st2);
     hipStreamWaitEvent(c->st, c->ev_join, 0);
     hipEventRecord(c->ev_j3, c->st3);
@@ -3302,7 +3187,6 @@ int svae_backward_imp(svae_ctx* c, void* stream) {
   c->Gr = c->m.shared ? c->Gimp_v : c->Gimp_pub;
   int r = engine_backward(c);
   if (c->side) {
-    side_merge(c);
     hipEventRecord(c->ev_join, c->st2);
     hipStreamWaitEvent(c->st, c->ev_join, 0);
     hipEventRecord(c->ev_j3, c->st3);

@@ -56,7 +56,6 @@ struct KwArgs {
   // launch-constant divisors (multiply-shift): the kernel's index decode has no integer divisions
   FastDiv d_win, d_pc, d_img, d_wr, d_rimg, d_q, d_qw;  // PR*PC, PC, Hr*Wr, Wr, R*Wr, (Ho/2)*(Wo/2), Wo/2
   int ntx, nty, ntz;  // tiles along rows / columns / (groups x classes)
-  int tpb;            // tiles per block: 1 = one tile per block (3-D grid); > 1 = persistent (1-D grid)
   int vec;            // 16-byte epilogue (every epilogue operand row 16-byte aligned; SVAE_KW_VEC)
   int ain_off;        // byte offset of the consumer-side BN table [3][Cin] in dynamic LDS (f.ain.acc != nullptr)
   int slot_off;       // NS = 2: byte offset of the [2][4] wave maxima of |A| in dynamic LDS
@@ -175,22 +174,19 @@ __device__ __forceinline__ void kw_epilogue_vec(const KwArgs& h, float* red, int
 // NS = 3: the split-bf16 mode (dtype bf16x6, opload.h split8 / mfma_split): the fp32 window is
 // staged as three bf16 planes (one LDS buffer, restaged under a second barrier per chunk) and every
 // A x B fragment pair runs the six plane products; B comes from the three shadow planes
-// PST: the persistent form (h.tpb > 1 tiles per block, 1-D grid); without it the tile loop runs once
 // BR: B fragments through a two-tap register ring (tap u + 1's loads issued under tap u's MFMAs; the
 // next chunk's first tap under the last) instead of a whole chunk of taps one chunk ahead: 16-tap
 // instances only; frees (NTW - 2) x TN x 2 x NS fragment registers (split mode: 48 VGPRs)
 // PI: window items per thread (npix * 4 <= 256 * PI); 3 frees 8 (fp32) window registers
 // AIN: the bf16-A instances that take the consumer-side BN (a bf16-stored pre-BN tensor); the fp32-A ones
 // take it at run time (in the bf16-A ones it would cost the default instances 12-15 spilled VGPRs)
-template <int BM, int BN, bool S2T, bool ABF, int NS = 1, bool PST = false, bool BR = false, int PI = KW_PI,
-          bool AIN = false>
-__global__ __launch_bounds__(256, AIN ? (S2T ? 4 : 3) : (ABF && BN == 32 && BM <= 64 && !PST) ? ((BR || S2T) ? KW_OCC_BR : KW_OCC)
+template <int BM, int BN, bool S2T, bool ABF, int NS = 1, bool BR = false, int PI = KW_PI, bool AIN = false>
+__global__ __launch_bounds__(256, AIN ? (S2T ? 4 : 3) : (ABF && BN == 32 && BM <= 64) ? ((BR || S2T) ? KW_OCC_BR : KW_OCC)
                                                                          : NS == 2 ? (BM == 128 ? KW_OCC_H16_128 : BM == 64 ? KW_OCC_H16_64 : KW_OCC_H16)
                                                                          : ((NS == 3 && BR) ? (BM == 32 ? KW_OCC_S32 : (BM == 128 ? 2 : 3)) : 2))
 void igemm_halo_kw_kernel(KwArgs h) {
   static_assert(NS == 1 || ((NS == 2 || NS == 3) && !ABF), "split planes from fp32 activations only");
   static_assert(!BR || !S2T, "the B ring: 16-tap instances");
-  static_assert(!(PST && NS == 2), "the fp16 planes' running exponent is per tile");
   constexpr int TM = BM / 32;
   constexpr int TN = BN / 32;
   constexpr int NTAP = S2T ? 4 : 16;
@@ -215,23 +211,11 @@ void igemm_halo_kw_kernel(KwArgs h) {
   const int nchunk = a.Cin / KW_CK;
   const int per_img = h.Hr * h.Wr;
 
-  // ---- tiles of this block: one (3-D XCD-ordered grid), or a contiguous run of tpb tiles of the
-  // linear order (x fastest, then y, then z) in the persistent form (1-D grid): tile i + 1's
-  // window and B fragments are loaded while tile i's last chunk computes and its epilogue runs ----
-  long long t_cur, t_end;
-  int bx, by, bz;
-  if constexpr (!PST) {
-    const BlockXYZ blk = xcd_block();
-    bx = blk.x; by = blk.y; bz = blk.z;
-    t_cur = 0; t_end = 1;
-  } else {
-    const long long ntiles = (long long)h.ntx * h.nty * h.ntz;
-    t_cur = (long long)blockIdx.x * h.tpb;
-    t_end = t_cur + h.tpb < ntiles ? t_cur + h.tpb : ntiles;
-    bx = (int)(t_cur % h.ntx); by = (int)((t_cur / h.ntx) % h.nty); bz = (int)(t_cur / ((long long)h.ntx * h.nty));
-  }
+  // ---- the tile of this block (3-D XCD-ordered grid) ----
+  const BlockXYZ blk = xcd_block();
+  const int bx = blk.x, by = blk.y, bz = blk.z;
 
-  // per-tile geometry (uniform): the current tile's, and the next one's while its loads are issued
+  // tile geometry (uniform)
   struct TileG {
     int m0, n0, group, cls, tap0;
   };
@@ -248,7 +232,7 @@ void igemm_halo_kw_kernel(KwArgs h) {
     }
     return q;
   };
-  // tap shift constants (the same for every tile of a launch)
+  // tap shift constants
   int toff0, tsgn;
   if (S2T) {
     toff0 = h.PC + 1;
@@ -378,7 +362,7 @@ void igemm_halo_kw_kernel(KwArgs h) {
     }
   };
 
-  // ---- A fragment bases: the whole BM-row tile, every wave (the same for every tile) ----
+  // ---- A fragment bases: the whole BM-row tile, every wave ----
   int abase[TM];
 #pragma unroll
   for (int tm = 0; tm < TM; ++tm) {
@@ -460,221 +444,180 @@ void igemm_halo_kw_kernel(KwArgs h) {
     __syncthreads();
   }
   KW_STAMP(1);
-  for (;;) {
-    // the next tile of this block (persistent form)
-    const bool has_tile = PST && t_cur + 1 < t_end;
-    TileG nxt = cur;
-    if (has_tile) {
-      const long long tn_ = t_cur + 1;
-      nxt = tile_geo((int)(tn_ % h.ntx), (int)((tn_ / h.ntx) % h.nty), (int)(tn_ / ((long long)h.ntx * h.nty)));
-    }
-    f32x16 acc[TM][TN];
+  f32x16 acc[TM][TN];
 #pragma unroll
-    for (int i = 0; i < TM; ++i)
+  for (int i = 0; i < TM; ++i)
 #pragma unroll
-      for (int j = 0; j < TN; ++j)
+    for (int j = 0; j < TN; ++j)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-    for (int c = 0; c < nchunk; ++c) {
-      const int buf = NS == 1 ? (c & 1) : 0;
-      const bool has_next = c + 1 < nchunk;
-      if constexpr (NS > 1) {  // one buffer of NS planes: stage chunk c, then prefetch c + 1
-        if constexpr (NS == 2) {
-          const int d = take_scale(c & 1);
-          if (d != 0) {
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-              for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = __builtin_ldexpf(acc[i][j][r], d);
-          }
-        }
-        store_window(0, c);
-        __syncthreads();
-      }
-      if (c < 4) KW_STAMP(2 + 2 * c);
-      if constexpr (!BR) {
-        if (has_next) {
-          load_window(cur, c + 1);
-        } else if (has_tile) {  // the next tile's first window, under this chunk's MFMAs and the epilogue
-          set_window(nxt);
-          load_window(nxt, 0);
-        }
-      }
-      const __bf16* W = ksm + buf * h.npix * KW_ROWP;
-#pragma unroll
-      for (int u = 0; u < NTW; ++u) {
-        if constexpr (BR) {  // the ring: the next tap's B (this chunk's, or the next chunk's first)
-          if (u + 1 < NTW) load_b(cur, (u + 1) & 1, u + 1, c);
-          else if (has_next) load_b(cur, (u + 1) & 1, 0, c + 1);
-          else if (has_tile) load_b(nxt, (u + 1) & 1, 0, 0);  // persistent: the next tile's first tap
-          // the next chunk's (or tile's) window after tap 1's B loads (in-order vmcnt: a later B wait
-          // also waits for it)
-          if (u == 0) {
-            if (has_next) {
-              load_window(cur, c + 1);
-            } else if (has_tile) {
-              set_window(nxt);
-              load_window(nxt, 0);
-            }
-          }
-        }
-        const int t = wave * NTW + u;
-        const int shift = S2T ? toff0 + tsgn * ((t >> 1) * h.PC + (t & 1)) : toff0 + tsgn * ((t >> 2) * h.PC + (t & 3));
-        const int sh = shift * KW_ROWP;
-#pragma unroll
-        for (int kq = 0; kq < 2; ++kq) {
-          bf16x8 af[TM][NS];
-#pragma unroll
-          for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-            for (int p = 0; p < NS; ++p) af[tm][p] = *(const bf16x8*)&W[p * h.npix * KW_ROWP + abase[tm] + sh + kq * 16];
-#pragma unroll
-          for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-            for (int tn = 0; tn < TN; ++tn) {
-              if constexpr (NS == 2) acc[tm][tn] = mfma_h16(af[tm], bq[BR ? (u & 1) : u][tn][kq], acc[tm][tn]);
-              else acc[tm][tn] = mfma_split<NS>(af[tm], bq[BR ? (u & 1) : u][tn][kq], acc[tm][tn]);
-            }
-        }
-        if constexpr (!BR) {
-          if (has_next) load_b(cur, u, u, c + 1);
-          else if (has_tile) load_b(nxt, u, u, 0);
-        }
-      }
-      if (c < 4) KW_STAMP(3 + 2 * c);
-      if constexpr (NS == 1) {
-        if (has_next) store_window(buf ^ 1, c + 1);
-      }
+  for (int c = 0; c < nchunk; ++c) {
+    const int buf = NS == 1 ? (c & 1) : 0;
+    const bool has_next = c + 1 < nchunk;
+    if constexpr (NS > 1) {  // one buffer of NS planes: stage chunk c, then prefetch c + 1
       if constexpr (NS == 2) {
-        if (has_next) wave_max_put((c + 1) & 1);
-      }
-      __syncthreads();
-    }
-    KW_STAMP(10);
-
-    // ---- sum the four waves' partial tiles in LDS (fixed order), then one epilogue ----
-    const int m0 = cur.m0, n0 = cur.n0, group = cur.group, cls = cur.cls;
-    float* red = (float*)ksm;  // [4][BM][BN]
-    [[maybe_unused]] int wex = H16_WS;  // the weight planes' exponent (split mode)
-    if constexpr (NS == 2) wex = a.wexp ? wtab_exp(a.wexp[group * a.wexp_gs]) : H16_WS;
+        const int d = take_scale(c & 1);
+        if (d != 0) {
 #pragma unroll
-    for (int tm = 0; tm < TM; ++tm)
+          for (int i = 0; i < TM; ++i)
 #pragma unroll
-      for (int tn = 0; tn < TN; ++tn)
+            for (int j = 0; j < TN; ++j)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int m = tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-          red[(wave * BM + m) * BN + tn * 32 + l32] = NS == 2 ? __builtin_ldexpf(acc[tm][tn][r], -(hs + wex)) : acc[tm][tn][r];
+              for (int r = 0; r < 16; ++r) acc[i][j][r] = __builtin_ldexpf(acc[i][j][r], d);
         }
-    __syncthreads();
-    KW_STAMP(11);
-    if (h.vec) {  // 16-byte epilogue: 4 consecutive columns per thread (write-through-friendly stores)
-      if (a.bw.pre_bf16) {
-        if (a.bw.y_bf16) kw_epilogue_vec<BM, BN, true, true>(h, red, tid, cur.m0, cur.n0, cur.group, cur.cls);
-        else kw_epilogue_vec<BM, BN, true, false>(h, red, tid, cur.m0, cur.n0, cur.group, cur.cls);
-      } else {
-        if (a.bw.y_bf16) kw_epilogue_vec<BM, BN, false, true>(h, red, tid, cur.m0, cur.n0, cur.group, cur.cls);
-        else kw_epilogue_vec<BM, BN, false, false>(h, red, tid, cur.m0, cur.n0, cur.group, cur.cls);
       }
-      KW_STAMP(12);
-      if (!has_tile) break;
+      store_window(0, c);
       __syncthreads();
-      cur = nxt;
-      ++t_cur;
-      if constexpr (NS == 1) {
-        store_window(0, 0);
-        __syncthreads();
+    }
+    if (c < 4) KW_STAMP(2 + 2 * c);
+    if constexpr (!BR) {
+      if (has_next) load_window(cur, c + 1);
+    }
+    const __bf16* W = ksm + buf * h.npix * KW_ROWP;
+#pragma unroll
+    for (int u = 0; u < NTW; ++u) {
+      if constexpr (BR) {  // the ring: the next tap's B (this chunk's, or the next chunk's first)
+        if (u + 1 < NTW) load_b(cur, (u + 1) & 1, u + 1, c);
+        else if (has_next) load_b(cur, (u + 1) & 1, 0, c + 1);
+        // the next chunk's window after tap 1's B loads (in-order vmcnt: a later B wait also waits for it)
+        if (u == 0 && has_next) load_window(cur, c + 1);
       }
-      continue;
-    }
-    constexpr int NRG = 256 / BN;  // row groups
-    const int col = tid % BN, rg = tid / BN;
-    const int n = n0 + col;
-    float* Cp = a.C + group * a.c_gs;
-    const float* bias = a.bias ? a.bias + group * a.bias_gs : nullptr;
-    const bool bwm = a.bw.pre != nullptr;
-    const bool bwc = bwm && n < a.bw.C;
-    float bm = 0.f, bi = 0.f, bb = 0.f;
-    if (bwc) {
-      bm = a.bw.mean[group * a.bw.ms_gs + n];
-      bi = a.bw.invstd[group * a.bw.ms_gs + n];
-      bb = a.bw.y ? 0.f : a.bw.beta[group * a.bw.beta_gs + n];
-    }
-    float s1 = 0.f, s2 = 0.f;
-    // every global load (accumulate target, BN-backward pre / y) before the first store: one
-    // memory round trip for the thread's BM / NRG rows, not one per row
-    constexpr int NR = BM / NRG;
-    long long orow[NR];
-    float cv[NR], pv[NR], yv[NR];
-    const bool pbf = a.bw.pre_bf16 != 0;
-    const float* bwpre = bwc ? pf_at(a.bw.pre, group * a.bw.pre_gs, pbf) : nullptr;
-    const bool ybf = a.bw.y_bf16 != 0;
-    const float* bwy = (bwc && a.bw.y) ? pf_at(a.bw.y, group * a.bw.y_gs, ybf) : nullptr;
-    const float biasv = bias ? bias[n] : 0.f;
+      const int t = wave * NTW + u;
+      const int shift = S2T ? toff0 + tsgn * ((t >> 1) * h.PC + (t & 1)) : toff0 + tsgn * ((t >> 2) * h.PC + (t & 3));
+      const int sh = shift * KW_ROWP;
 #pragma unroll
-    for (int i = 0; i < NR; ++i) {
-      orow[i] = kw_out_row(h, g, cls, m0 + rg + i * NRG);
-      cv[i] = a.accumulate ? Cp[orow[i] * a.ldc + n] : 0.f;
-      pv[i] = bwpre ? pf_ld(bwpre, orow[i] * a.bw.ldp + n, pbf) : 0.f;
-      yv[i] = bwy ? pf_ld(bwy, orow[i] * a.bw.ldy + n, ybf) : 0.f;
-    }
+      for (int kq = 0; kq < 2; ++kq) {
+        bf16x8 af[TM][NS];
 #pragma unroll
-    for (int i = 0; i < NR; ++i) {
-      const int m = rg + i * NRG;
-      float v = red[(0 * BM + m) * BN + col];
+        for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
-      for (int w = 1; w < 4; ++w) v += red[(w * BM + m) * BN + col];
-      if (a.c_bf16) v = bf_rnd(v);  // bf16-stored pre-BN output: the statistics of the stored values
-      if (!bwm) {
-        s1 += v;
-        s2 += v * v;
-      }
-      if (bias) v += biasv;
-      v = act_f(v, a.act);
-      if (a.accumulate) v += cv[i];
-      if (a.c_bf16) ((__bf16*)a.C)[group * a.c_gs + orow[i] * a.ldc + n] = (__bf16)v;
-#ifdef SVAE_EXP_NOSTORE  // timing experiment (wrong results): the epilogue without its stores
-      else if (v != v) st_out(&Cp[orow[i] * a.ldc + n], v);
-#else
-      else st_out(&Cp[orow[i] * a.ldc + n], v);
-#endif
-      if (bwc) bw_term_v(v, pv[i], bm, bi, bb, bwy != nullptr, yv[i], a.bw.act, s1, s2);
-    }
-    KW_STAMP(15);
-    if (a.stats) {
-      __syncthreads();  // every wave is done reading red
-      red[tid] = s1;
-      red[256 + tid] = s2;
-      __syncthreads();
-      if (tid < BN) {
-        const int SC = bwm ? a.bw.C : a.N;  // stats columns (row-block stride 2*SC)
-        if (n0 + tid < SC) {
-          float s = 0.f, q = 0.f;
+          for (int p = 0; p < NS; ++p) af[tm][p] = *(const bf16x8*)&W[p * h.npix * KW_ROWP + abase[tm] + sh + kq * 16];
 #pragma unroll
-          for (int j = 0; j < NRG; ++j) {
-            s += red[j * BN + tid];
-            q += red[256 + j * BN + tid];
+        for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+          for (int tn = 0; tn < TN; ++tn) {
+            if constexpr (NS == 2) acc[tm][tn] = mfma_h16(af[tm], bq[BR ? (u & 1) : u][tn][kq], acc[tm][tn]);
+            else acc[tm][tn] = mfma_split<NS>(af[tm], bq[BR ? (u & 1) : u][tn][kq], acc[tm][tn]);
           }
-          const int rb = cls * h.ntx + m0 / BM;
-          stat_put(a.stats + (rb & (a.s_nsh - 1)) * a.s_sh + group * a.s_gs, n0 + tid, s, q);
-        }
       }
-      if (a.fin.cnt) bn_fin_arrive(a.fin, group, (int*)red);
+      if constexpr (!BR) {
+        if (has_next) load_b(cur, u, u, c + 1);
+      }
+    }
+    if (c < 4) KW_STAMP(3 + 2 * c);
+    if constexpr (NS == 1) {
+      if (has_next) store_window(buf ^ 1, c + 1);
+    }
+    if constexpr (NS == 2) {
+      if (has_next) wave_max_put((c + 1) & 1);
+    }
+    __syncthreads();
+  }
+  KW_STAMP(10);
+
+  // ---- sum the four waves' partial tiles in LDS (fixed order), then one epilogue ----
+  const int m0 = cur.m0, n0 = cur.n0, group = cur.group, cls = cur.cls;
+  float* red = (float*)ksm;  // [4][BM][BN]
+  [[maybe_unused]] int wex = H16_WS;  // the weight planes' exponent (split mode)
+  if constexpr (NS == 2) wex = a.wexp ? wtab_exp(a.wexp[group * a.wexp_gs]) : H16_WS;
+#pragma unroll
+  for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+    for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int m = tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+        red[(wave * BM + m) * BN + tn * 32 + l32] = NS == 2 ? __builtin_ldexpf(acc[tm][tn][r], -(hs + wex)) : acc[tm][tn][r];
+      }
+  __syncthreads();
+  KW_STAMP(11);
+  if (h.vec) {  // 16-byte epilogue: 4 consecutive columns per thread (write-through-friendly stores)
+    if (a.bw.pre_bf16) {
+      if (a.bw.y_bf16) kw_epilogue_vec<BM, BN, true, true>(h, red, tid, cur.m0, cur.n0, cur.group, cur.cls);
+      else kw_epilogue_vec<BM, BN, true, false>(h, red, tid, cur.m0, cur.n0, cur.group, cur.cls);
+    } else {
+      if (a.bw.y_bf16) kw_epilogue_vec<BM, BN, false, true>(h, red, tid, cur.m0, cur.n0, cur.group, cur.cls);
+      else kw_epilogue_vec<BM, BN, false, false>(h, red, tid, cur.m0, cur.n0, cur.group, cur.cls);
     }
     KW_STAMP(12);
-    if (!has_tile) break;
-    // ---- the next tile: its window (prefetched above) into LDS once every wave is done with red ----
-    __syncthreads();
-    cur = nxt;
-    ++t_cur;
-    if constexpr (NS == 1) {
-      store_window(0, 0);
-      __syncthreads();
-    }
+    return;
   }
+  constexpr int NRG = 256 / BN;  // row groups
+  const int col = tid % BN, rg = tid / BN;
+  const int n = n0 + col;
+  float* Cp = a.C + group * a.c_gs;
+  const float* bias = a.bias ? a.bias + group * a.bias_gs : nullptr;
+  const bool bwm = a.bw.pre != nullptr;
+  const bool bwc = bwm && n < a.bw.C;
+  float bm = 0.f, bi = 0.f, bb = 0.f;
+  if (bwc) {
+    bm = a.bw.mean[group * a.bw.ms_gs + n];
+    bi = a.bw.invstd[group * a.bw.ms_gs + n];
+    bb = a.bw.y ? 0.f : a.bw.beta[group * a.bw.beta_gs + n];
+  }
+  float s1 = 0.f, s2 = 0.f;
+  // every global load (accumulate target, BN-backward pre / y) before the first store: one
+  // memory round trip for the thread's BM / NRG rows, not one per row
+  constexpr int NR = BM / NRG;
+  long long orow[NR];
+  float cv[NR], pv[NR], yv[NR];
+  const bool pbf = a.bw.pre_bf16 != 0;
+  const float* bwpre = bwc ? pf_at(a.bw.pre, group * a.bw.pre_gs, pbf) : nullptr;
+  const bool ybf = a.bw.y_bf16 != 0;
+  const float* bwy = (bwc && a.bw.y) ? pf_at(a.bw.y, group * a.bw.y_gs, ybf) : nullptr;
+  const float biasv = bias ? bias[n] : 0.f;
+#pragma unroll
+  for (int i = 0; i < NR; ++i) {
+    orow[i] = kw_out_row(h, g, cls, m0 + rg + i * NRG);
+    cv[i] = a.accumulate ? Cp[orow[i] * a.ldc + n] : 0.f;
+    pv[i] = bwpre ? pf_ld(bwpre, orow[i] * a.bw.ldp + n, pbf) : 0.f;
+    yv[i] = bwy ? pf_ld(bwy, orow[i] * a.bw.ldy + n, ybf) : 0.f;
+  }
+#pragma unroll
+  for (int i = 0; i < NR; ++i) {
+    const int m = rg + i * NRG;
+    float v = red[(0 * BM + m) * BN + col];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) v += red[(w * BM + m) * BN + col];
+    if (a.c_bf16) v = bf_rnd(v);  // bf16-stored pre-BN output: the statistics of the stored values
+    if (!bwm) {
+      s1 += v;
+      s2 += v * v;
+    }
+    if (bias) v += biasv;
+    v = act_f(v, a.act);
+    if (a.accumulate) v += cv[i];
+    if (a.c_bf16) ((__bf16*)a.C)[group * a.c_gs + orow[i] * a.ldc + n] = (__bf16)v;
+#ifdef SVAE_EXP_NOSTORE  // timing experiment (wrong results): the epilogue without its stores
+    else if (v != v) st_out(&Cp[orow[i] * a.ldc + n], v);
+#else
+    else st_out(&Cp[orow[i] * a.ldc + n], v);
+#endif
+    if (bwc) bw_term_v(v, pv[i], bm, bi, bb, bwy != nullptr, yv[i], a.bw.act, s1, s2);
+  }
+  KW_STAMP(15);
+  if (a.stats) {
+    __syncthreads();  // every wave is done reading red
+    red[tid] = s1;
+    red[256 + tid] = s2;
+    __syncthreads();
+    if (tid < BN) {
+      const int SC = bwm ? a.bw.C : a.N;  // stats columns (row-block stride 2*SC)
+      if (n0 + tid < SC) {
+        float s = 0.f, q = 0.f;
+#pragma unroll
+        for (int j = 0; j < NRG; ++j) {
+          s += red[j * BN + tid];
+          q += red[256 + j * BN + tid];
+        }
+        const int rb = cls * h.ntx + m0 / BM;
+        stat_put(a.stats + (rb & (a.s_nsh - 1)) * a.s_sh + group * a.s_gs, n0 + tid, s, q);
+      }
+    }
+    if (a.fin.cnt) bn_fin_arrive(a.fin, group, (int*)red);
+  }
+  KW_STAMP(12);
 }
 
 }  // namespace
@@ -776,7 +719,6 @@ int halo_kw(const FwdArgs& a, int groups, hipStream_t s) {
   h.ntx = (int)grid.x;
   h.nty = (int)grid.y;
   h.ntz = (int)grid.z;
-  h.tpb = 1;
   h.ain_off = 0;
   h.slot_off = 0;
   if (a.ain.acc) {  // the consumer-side BN table [3][Cin] after the window / reduction region
@@ -796,20 +738,6 @@ int halo_kw(const FwdArgs& a, int groups, hipStream_t s) {
            (a.bw.y ? (a.bw.ldy % 4 == 0 && a.bw.y_gs % 4 == 0 && al16(a.bw.y)) : (al16(a.bw.beta) && a.bw.beta_gs % 4 == 0));
     h.vec = ok ? 1 : 0;
   }
-  // persistent form (SVAE_KW_PERSIST=1): where the tiles exceed the resident blocks, each block runs
-  // a contiguous run of tiles with the next tile's window / B loads under the current tile's last
-  // chunk and epilogue
-  static const int persist = svae_knob("SVAE_KW_PERSIST", 0);
-  if (persist && a.nsp <= 1 && a.a_bf16 && bn == 32 && bm == 64 && !a.ain.acc) {  // the persistent instances
-    const int occ_w = 2;
-    const int occ_l = (int)std::max<size_t>(1, (size_t)163840 / std::max<size_t>(lds, 1));
-    const long long slots = 256LL * std::min(occ_w, occ_l) * (persist > 1 ? persist : 1);
-    const long long ntiles = (long long)h.ntx * h.nty * h.ntz;
-    if (ntiles > slots) {
-      h.tpb = (int)((ntiles + slots - 1) / slots);
-      grid = dim3((unsigned)((ntiles + h.tpb - 1) / h.tpb), 1, 1);
-    }
-  }
   // SVAE_KW_BRING: the two-tap B register ring on the 16-tap instances (bit 0: split mode, bit 1: bf16).
   // Default 1: the split instances go from 2 to 3 waves per SIMD (bf16x6 step 18.74 -> 18.08 ms,
   // profiles/r04_ab1.txt); the bf16 ones would need a fifth wave and spill (8 % slower)
@@ -820,11 +748,11 @@ int halo_kw(const FwdArgs& a, int groups, hipStream_t s) {
       for (const void* f : {(const void*)igemm_halo_kw_kernel<64, 32, true, false, 2>,
                             (const void*)igemm_halo_kw_kernel<32, 32, true, false, 2>,
                             (const void*)igemm_halo_kw_kernel<128, 32, true, false, 2>,
-                            (const void*)igemm_halo_kw_kernel<64, 32, false, false, 2, false, true, 3>,
-                            (const void*)igemm_halo_kw_kernel<32, 32, false, false, 2, false, true, 3>,
-                            (const void*)igemm_halo_kw_kernel<64, 32, false, false, 2, false, true>,
-                            (const void*)igemm_halo_kw_kernel<32, 32, false, false, 2, false, true>,
-                            (const void*)igemm_halo_kw_kernel<128, 32, false, false, 2, false, true>})
+                            (const void*)igemm_halo_kw_kernel<64, 32, false, false, 2, true, 3>,
+                            (const void*)igemm_halo_kw_kernel<32, 32, false, false, 2, true, 3>,
+                            (const void*)igemm_halo_kw_kernel<64, 32, false, false, 2, true>,
+                            (const void*)igemm_halo_kw_kernel<32, 32, false, false, 2, true>,
+                            (const void*)igemm_halo_kw_kernel<128, 32, false, false, 2, true>})
         hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 98304);
       attr = true;
     }
@@ -834,15 +762,15 @@ int halo_kw(const FwdArgs& a, int groups, hipStream_t s) {
     const bool pi3 = h.npix * 4 <= 256 * 3;
     if (bm == 128) {
       if (s2t) hipLaunchKernelGGL((igemm_halo_kw_kernel<128, 32, true, false, 2>), grid, dim3(256), lds, s, h);
-      else hipLaunchKernelGGL((igemm_halo_kw_kernel<128, 32, false, false, 2, false, true>), grid, dim3(256), lds, s, h);
+      else hipLaunchKernelGGL((igemm_halo_kw_kernel<128, 32, false, false, 2, true>), grid, dim3(256), lds, s, h);
     } else if (bm == 64) {
       if (s2t) hipLaunchKernelGGL((igemm_halo_kw_kernel<64, 32, true, false, 2>), grid, dim3(256), lds, s, h);
-      else if (pi3) hipLaunchKernelGGL((igemm_halo_kw_kernel<64, 32, false, false, 2, false, true, 3>), grid, dim3(256), lds, s, h);
-      else hipLaunchKernelGGL((igemm_halo_kw_kernel<64, 32, false, false, 2, false, true>), grid, dim3(256), lds, s, h);
+      else if (pi3) hipLaunchKernelGGL((igemm_halo_kw_kernel<64, 32, false, false, 2, true, 3>), grid, dim3(256), lds, s, h);
+      else hipLaunchKernelGGL((igemm_halo_kw_kernel<64, 32, false, false, 2, true>), grid, dim3(256), lds, s, h);
     } else {
       if (s2t) hipLaunchKernelGGL((igemm_halo_kw_kernel<32, 32, true, false, 2>), grid, dim3(256), lds, s, h);
-      else if (pi3) hipLaunchKernelGGL((igemm_halo_kw_kernel<32, 32, false, false, 2, false, true, 3>), grid, dim3(256), lds, s, h);
-      else hipLaunchKernelGGL((igemm_halo_kw_kernel<32, 32, false, false, 2, false, true>), grid, dim3(256), lds, s, h);
+      else if (pi3) hipLaunchKernelGGL((igemm_halo_kw_kernel<32, 32, false, false, 2, true, 3>), grid, dim3(256), lds, s, h);
+      else hipLaunchKernelGGL((igemm_halo_kw_kernel<32, 32, false, false, 2, true>), grid, dim3(256), lds, s, h);
     }
     return a.nclass * (a.rows / bm);
   }
@@ -853,63 +781,41 @@ int halo_kw(const FwdArgs& a, int groups, hipStream_t s) {
                             (const void*)igemm_halo_kw_kernel<64, 32, false, false, 3>,
                             (const void*)igemm_halo_kw_kernel<32, 32, true, false, 3>,
                             (const void*)igemm_halo_kw_kernel<32, 32, false, false, 3>,
-                            (const void*)igemm_halo_kw_kernel<64, 32, false, false, 3, false, true>,
-                            (const void*)igemm_halo_kw_kernel<32, 32, false, false, 3, false, true>,
-                            (const void*)igemm_halo_kw_kernel<64, 32, false, false, 3, false, true, 3>,
-                            (const void*)igemm_halo_kw_kernel<32, 32, false, false, 3, false, true, 3>,
+                            (const void*)igemm_halo_kw_kernel<64, 32, false, false, 3, true>,
+                            (const void*)igemm_halo_kw_kernel<32, 32, false, false, 3, true>,
+                            (const void*)igemm_halo_kw_kernel<64, 32, false, false, 3, true, 3>,
+                            (const void*)igemm_halo_kw_kernel<32, 32, false, false, 3, true, 3>,
                             (const void*)igemm_halo_kw_kernel<128, 32, true, false, 3>,
-                            (const void*)igemm_halo_kw_kernel<128, 32, false, false, 3, false, true>})
+                            (const void*)igemm_halo_kw_kernel<128, 32, false, false, 3, true>})
         hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 98304);
       attr = true;
     }
     const bool br = (bring & 1) != 0;
     const bool pi3 = h.npix * 4 <= 256 * 3 && split_pi3();
-    // SVAE_KW_PERSIST_SPLIT=k: the 64-row split ring instances persistent over 256 x 3 x k blocks (the
-    // next tile's window and first B fragments load under the current tile's last chunk)
-    static const int persist_split = svae_knob("SVAE_KW_PERSIST_SPLIT", 0);
-    if (persist_split && br && pi3 && bm == 64 && !s2t && !a.ain.acc) {
-      const long long slots = 256LL * 3 * persist_split;
-      const long long ntiles = (long long)h.ntx * h.nty * h.ntz;
-      if (ntiles > slots) {
-        h.tpb = (int)((ntiles + slots - 1) / slots);
-        grid = dim3((unsigned)((ntiles + h.tpb - 1) / h.tpb), 1, 1);
-        static bool attrp = false;
-        if (!attrp) {
-          hipFuncSetAttribute((const void*)igemm_halo_kw_kernel<64, 32, false, false, 3, true, true, 3>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 98304);
-          attrp = true;
-        }
-        hipLaunchKernelGGL((igemm_halo_kw_kernel<64, 32, false, false, 3, true, true, 3>), grid, dim3(256), lds, s, h);
-        return a.nclass * (a.rows / bm);
-      }
-    }
     if (bm == 128) {  // 128-row tiles: each B fragment serves four row fragments
       if (s2t) hipLaunchKernelGGL((igemm_halo_kw_kernel<128, 32, true, false, 3>), grid, dim3(256), lds, s, h);
-      else hipLaunchKernelGGL((igemm_halo_kw_kernel<128, 32, false, false, 3, false, true>), grid, dim3(256), lds, s, h);
+      else hipLaunchKernelGGL((igemm_halo_kw_kernel<128, 32, false, false, 3, true>), grid, dim3(256), lds, s, h);
     } else if (bm == 64) {
       if (s2t) hipLaunchKernelGGL((igemm_halo_kw_kernel<64, 32, true, false, 3>), grid, dim3(256), lds, s, h);
-      else if (br && pi3) hipLaunchKernelGGL((igemm_halo_kw_kernel<64, 32, false, false, 3, false, true, 3>), grid, dim3(256), lds, s, h);
-      else if (br) hipLaunchKernelGGL((igemm_halo_kw_kernel<64, 32, false, false, 3, false, true>), grid, dim3(256), lds, s, h);
+      else if (br && pi3) hipLaunchKernelGGL((igemm_halo_kw_kernel<64, 32, false, false, 3, true, 3>), grid, dim3(256), lds, s, h);
+      else if (br) hipLaunchKernelGGL((igemm_halo_kw_kernel<64, 32, false, false, 3, true>), grid, dim3(256), lds, s, h);
       else hipLaunchKernelGGL((igemm_halo_kw_kernel<64, 32, false, false, 3>), grid, dim3(256), lds, s, h);
     } else {
       if (s2t) hipLaunchKernelGGL((igemm_halo_kw_kernel<32, 32, true, false, 3>), grid, dim3(256), lds, s, h);
-      else if (br && pi3) hipLaunchKernelGGL((igemm_halo_kw_kernel<32, 32, false, false, 3, false, true, 3>), grid, dim3(256), lds, s, h);
-      else if (br) hipLaunchKernelGGL((igemm_halo_kw_kernel<32, 32, false, false, 3, false, true>), grid, dim3(256), lds, s, h);
+      else if (br && pi3) hipLaunchKernelGGL((igemm_halo_kw_kernel<32, 32, false, false, 3, true, 3>), grid, dim3(256), lds, s, h);
+      else if (br) hipLaunchKernelGGL((igemm_halo_kw_kernel<32, 32, false, false, 3, true>), grid, dim3(256), lds, s, h);
       else hipLaunchKernelGGL((igemm_halo_kw_kernel<32, 32, false, false, 3>), grid, dim3(256), lds, s, h);
     }
     return a.nclass * (a.rows / bm);
   }
 #define KW_LAUNCH(BM_, BN_)                                                                                  \
-  if (h.tpb > 1 && a.a_bf16 && BN_ == 32 && BM_ == 64) {  /* persistent: the bf16-A 64x32 instances */     \
-    if (s2t) hipLaunchKernelGGL((igemm_halo_kw_kernel<64, 32, true, true, 1, true>), grid, dim3(256), lds, s, h); \
-    else hipLaunchKernelGGL((igemm_halo_kw_kernel<64, 32, false, true, 1, true>), grid, dim3(256), lds, s, h);    \
-  } else if (a.a_bf16 && a.ain.acc) {  /* consumer-side BN of a bf16 pre-BN tensor (halo_kw_plan: BN 32, BM <= 64) */ \
-    if (s2t) hipLaunchKernelGGL((igemm_halo_kw_kernel<BM_, BN_, true, true, 1, false, false, KW_PI, true>), grid, dim3(256), lds, s, h); \
-    else hipLaunchKernelGGL((igemm_halo_kw_kernel<BM_, BN_, false, true, 1, false, false, KW_PI, true>), grid, dim3(256), lds, s, h); \
+  if (a.a_bf16 && a.ain.acc) {  /* consumer-side BN of a bf16 pre-BN tensor (halo_kw_plan: BN 32, BM <= 64) */ \
+    if (s2t) hipLaunchKernelGGL((igemm_halo_kw_kernel<BM_, BN_, true, true, 1, false, KW_PI, true>), grid, dim3(256), lds, s, h); \
+    else hipLaunchKernelGGL((igemm_halo_kw_kernel<BM_, BN_, false, true, 1, false, KW_PI, true>), grid, dim3(256), lds, s, h); \
   } else if (a.a_bf16) {                                                                                     \
     if (s2t) hipLaunchKernelGGL((igemm_halo_kw_kernel<BM_, BN_, true, true>), grid, dim3(256), lds, s, h);    \
     else if ((bring & 2) && BN_ == 32 && BM_ <= 64)                                                          \
-      hipLaunchKernelGGL((igemm_halo_kw_kernel<BM_, BN_, false, true, 1, false, true>), grid, dim3(256), lds, s, h); \
+      hipLaunchKernelGGL((igemm_halo_kw_kernel<BM_, BN_, false, true, 1, true>), grid, dim3(256), lds, s, h); \
     else hipLaunchKernelGGL((igemm_halo_kw_kernel<BM_, BN_, false, true>), grid, dim3(256), lds, s, h);       \
   } else {                                                                                                   \
     if (s2t) hipLaunchKernelGGL((igemm_halo_kw_kernel<BM_, BN_, true, false>), grid, dim3(256), lds, s, h);   \

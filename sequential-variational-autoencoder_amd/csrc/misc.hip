@@ -405,11 +405,6 @@ __global__ __launch_bounds__(256) void heads_fwd_kernel(const float* __restrict_
 
 int heads_splits(int K) { return (K + HF_CHUNK - 1) / HF_CHUNK; }
 
-static bool heads_narrow_off() {  // SVAE_HEADS_SKINNY=1: the former 4-row skinny pass (A/B)
-  static const bool v = svae_knob("SVAE_HEADS_SKINNY", 0) == 1;
-  return v;
-}
-
 // Wide heads (4 < D <= 32, e.g. LSUN's 20-30 latents per level): a block owns 64 batch rows x both heads'
 // 2D outputs (padded to 64) over one HF_CHUNK split of K, staged through LDS 32 k at a time; each thread
 // keeps a 4 x 4 output tile.  The weights of a split are read once per 64 rows (skinny_kernel<32> read
@@ -490,7 +485,7 @@ void heads_fwd(const float* X, long long x_gs, int B, int K, const float* Wm, co
   // mean and stddev heads in one pass over X (the shared recognition features)
   const bool al = ((uintptr_t)X % 16 == 0) && ((uintptr_t)Wm % 16 == 0) && ((uintptr_t)Ws % 16 == 0) &&
                   (x_gs % 4 == 0) && (w_gs % 4 == 0);
-  if (D <= 4 && K % 4 == 0 && al && !heads_narrow_off()) {
+  if (D <= 4 && K % 4 == 0 && al) {
     dim3 grid((B + HF_ROWS - 1) / HF_ROWS, heads_splits(K), groups);
     const int c2 = pcols / 2 + coff;
 #define HF_L(DD) hipLaunchKernelGGL(heads_fwd_kernel<DD>, grid, dim3(256), 0, s, X, x_gs, B, K, Wm, Ws, w_gs, part, \

@@ -310,10 +310,9 @@ void wh2_launch_op(const WH2Args& a, int groups, hipStream_t s) {
                      dim3(64 * KYR * WN * WK), lds, s, a);
 }
 // operand storage (G fp32/bf16 x D fp32/bf16) as a compile-time parameter: no branches in the loads
-int env_int(const char* name, int dflt);
 template <int WO, int CP, int KYR, int WN, int WK, bool DB, int OPB, int NSW, int S>
 void wh2_launch_pf(const WH2Args& a, int groups, hipStream_t s) {
-  static const int pf = env_int("SVAE_WH2_PF", 2);  // register prefetch depth in chunks (1 or 2)
+  static const int pf = svae_knob("SVAE_WH2_PF", 2);  // register prefetch depth in chunks (1 or 2)
   if (pf == 1) wh2_launch_op<WO, CP, KYR, WN, WK, DB, OPB, NSW, 1, S>(a, groups, s);
   else wh2_launch_op<WO, CP, KYR, WN, WK, DB, OPB, NSW, 2, S>(a, groups, s);
 }
@@ -331,13 +330,11 @@ void wh2_launch(const WH2Args& a, int groups, hipStream_t s) {
   }
 }
 
-int env_int(const char* name, int dflt) { return svae_knob(name, dflt); }
-
 }  // namespace
 
 int wgrad_halo2_enabled() {
   static int v = -1;
-  if (v < 0) v = env_int("SVAE_NO_WH2", 0) ? 0 : 1;
+  if (v < 0) v = svae_knob("SVAE_NO_WH2", 0) ? 0 : 1;
   return v;
 }
 
@@ -352,7 +349,7 @@ int wgrad_halo2_enabled() {
 // chunks (the window is ~4x the chunk's pixels), row-space widths 8 and 16
 static int wh2_cp(int WO, int S) { return S == 2 ? 64 : (WO == 32 ? 128 : 256); }
 static int wh2_s2_enabled() {
-  static const int v = env_int("SVAE_WH2_S2", 1);
+  static const int v = svae_knob("SVAE_WH2_S2", 1);
   return v;
 }
 
@@ -375,18 +372,18 @@ int wgrad_halo2(const WgArgs& w, int groups, float* slab, long long slab_cap, fl
   const int S = w.g.stride;
   // split mode (NSP = 2, fp32 operands): 128-pixel chunks for the 8- and 16-wide layers halve the
   // staging registers (256 VGPRs + spills at 256-pixel chunks; SVAE_WH2_SPLIT_CP=256 restores them)
-  static const int split_cp = env_int("SVAE_WH2_SPLIT_CP", 128);
+  static const int split_cp = svae_knob("SVAE_WH2_SPLIT_CP", 128);
   const bool sp128 = w.nsp > 1 && S == 1 && WO <= 16 && split_cp == 128 && w.rows % 128 == 0;
   const int cp = sp128 ? 128 : wh2_cp(WO, S);
   // split mode: 128 (its weight-GEMMs are 3x the MFMA work, so more splits spread the side stream: parity
   // mode +1.9 %, profiles/r04_knobs_ab.txt); bf16: 96 (+0.6 %, profiles/r04_knobs2_ab.txt).  SVAE_WH2_TARGET
   // overrides both
-  static const int target_env = env_int("SVAE_WH2_TARGET", 0);
+  static const int target_env = svae_knob("SVAE_WH2_TARGET", 0);
   const int target = target_env > 0 ? target_env : target_blocks > 0 ? target_blocks : (w.nsp > 1 ? 128 : 96);
-  static const int minch = env_int("SVAE_WH2_MINCH", 4);
+  static const int minch = svae_knob("SVAE_WH2_MINCH", 4);
   // SVAE_WH2_NSW=2: a 64-column block as 4 waves of two 32-column subtiles (each transposed A
   // fragment feeds two MFMAs) instead of 8 waves of one
-  static const int nsw = env_int("SVAE_WH2_NSW", 1);
+  static const int nsw = svae_knob("SVAE_WH2_NSW", 1);
   const int wn = (w.N % 64 == 0) ? 2 : 1;
   const int kyr = 4;
   WH2Args a;
