@@ -266,6 +266,60 @@ int svae_op_bn_act_bwd(const float* dy, const float* y, const float* x, int64_t 
                        void* stream);
 /* y[B,N] = x[B,K] @ w[K,N]  (fully_connected, no bias) */
 int svae_op_fc(const float* x, int b, int k, const float* w, int nout, float* y, void* stream);
+/* ---- recognition heads, latent and split-latent kernels (csrc/misc.hip), each through the engine's own
+ * launcher.  Device pointers unless said otherwise, the caller's stream, no allocation.  SVAE_EBADARG: a
+ * null pointer, a non-positive size, d > 32 (heads), Dz > 256 (latent), k > 32 (split-latent), or what
+ * the entry says below.  "groups" is the engine's T-batched recognition: group g of a tensor lies one
+ * group stride after group g - 1. ---- */
+/* number of K splits the heads forward writes: ceil(k / 2048) (pure host) */
+int svae_op_heads_splits(int k);
+/* kernel taken by a heads launch (reported through *variant, which may be NULL) */
+enum { SVAE_HEADS_FWD_NARROW = 0, SVAE_HEADS_FWD_TILE = 1, SVAE_HEADS_FWD_SKINNY = 2 };
+enum { SVAE_HEADS_BWD_ROWGROUP = 0, SVAE_HEADS_BWD_PLAIN = 1, SVAE_HEADS_BWD_TILE = 2 };
+/* Partial products of both heads of one level: x [groups][b][k], wm and ws [k][d] per group, w_gs elements
+ * apart; part [groups][nsplit][b][pcols].  Split s < svae_op_heads_splits(k) of row n receives
+ * sum_{kk in split s} x[n][kk] * wm[kk][o] at column coff + o and the ws sum at column pcols / 2 + coff + o;
+ * nothing else of part is written (rows past the level's own splits stay as they are: the latent forward
+ * sums all nsplit rows, so the caller keeps them zero).  SVAE_EBADARG also for nsplit <
+ * svae_op_heads_splits(k), an odd pcols, or coff + d > pcols / 2. */
+int svae_op_heads_fwd(const float* x, int b, int k, const float* wm, const float* ws, int64_t w_gs, int d, float* part,
+                      int nsplit, int pcols, int coff, int groups, int32_t* variant, void* stream);
+/* Latent of a step from the head partials: part [groups][nsplit][b][2*Dz] with Dz = sum of dims[levels]
+ * (dims: HOST pointer, 1 <= levels <= 8), eps, mu, sig, z [groups][b][Dz], kl_img [groups][b].  Biases bm, bs
+ * [groups][Dz + levels * bias_gap]: every level's biases are a tensor of their own in the engine, so level l's
+ * start bias_gap (>= 0) floats after the end of level l - 1's, and the first level's at the group's start.
+ * mu = sum_s part + bm (raw), sig = sigmoid(sum_s part + bs), z = clamp(mu, +-clip) + sig * eps, kl_img =
+ * mean_d(-0.5 - log sig + (sig^2 + clamp(mu)^2) / (2 prior^2)), or mean_d(-log sig) when uniform != 0. */
+int svae_op_latent_fwd(const float* part, int nsplit, int b, int levels, const int32_t* dims, const float* bm,
+                       const float* bs, int bias_gap, float clip, float prior, int uniform, const float* eps,
+                       float* mu, float* sig, float* z, float* kl_img, int groups, void* stream);
+/* Its backward: dhead [groups][b][2*Dz] = gradient of sum(dz * z) + kl_coef[g] * sum_n kl_img[n] with
+ * respect to the raw mean (columns 0 .. Dz - 1; zero where |mu| > clip) and to the pre-sigmoid value
+ * (columns Dz ..).  kl_coef: device, one float per group. */
+int svae_op_latent_bwd(const float* mu, const float* sig, const float* eps, const float* dz, int b, int dz_dim,
+                       const float* kl_coef, float prior, int uniform, float clip, float* dhead, int groups,
+                       void* stream);
+/* Heads backward of one level from columns coff .. coff + d - 1 (mean) and dcols / 2 + coff .. (stddev) of
+ * dhead [groups][b][dcols]: dx [groups][b][k] = (accumulate ? dx : 0) + dhead_l @ [wm | ws]^T, dwm, dws
+ * [k][d] = x^T dhead_l, dbm, dbs [d] = sum_n dhead_l.  wm, ws, dwm, dws, dbm and dbs all step w_gs elements
+ * per group. */
+int svae_op_heads_bwd(const float* x, float* dx, int b, int k, const float* wm, const float* ws, int64_t w_gs, int d,
+                      const float* dhead, int dcols, int coff, float* dwm, float* dws, float* dbm, float* dbs,
+                      int accumulate, int groups, int32_t* variant, void* stream);
+/* split_latent level: out = lrelu_0.1(BN_batch(z[:, zoff : zoff + k] @ w) + beta) (biased variance, eps
+ * 1e-3) for z [b][ldz], w [k][j], beta, mean, invstd [j]; element (n, jj) is written at
+ * out + n * o_n + (jj / f) * ldo + jj % f.  nt == 1: one launch.  1 < nt <= 16: the chain's one launch over nt
+ * steps; step i reads z + i * z_ts, w + i * w_ts, beta + i * bn_ts and writes mean / invstd + i * bn_ts and
+ * out + i * out_ts. */
+int svae_op_splitfc(const float* z, int ldz, int zoff, int b, int k, const float* w, const float* beta, int j, int f,
+                    int ldo, int64_t o_n, float* mean, float* invstd, float* out, int nt, int64_t z_ts, int64_t w_ts,
+                    int64_t bn_ts, int64_t out_ts, void* stream);
+/* Its backward from dout (addressed like out) and the forward's mean / invstd: dw [k][j], dbeta [j], and
+ * dz[n][zoff + kk] += the input gradient (dz [b][ldz]; the block partials go through scratch, at least
+ * ceil(j / 64) * b * k floats). */
+int svae_op_splitfc_bwd(const float* z, int ldz, int zoff, int b, int k, const float* w, const float* beta, int j,
+                        int f, int ldo, int64_t o_n, const float* mean, const float* invstd, const float* dout,
+                        float* dw, float* dbeta, float* dz, void* scratch, int64_t scratch_bytes, void* stream);
 /* The training batch in one launch on `stream` (no allocation, no synchronisation): rows of a
  * device-resident dataset data [N, per_image] (uint8 when data_u8 = 1, else fp32) are gathered,
  * dequantised into the clean `target` and corrupted into the denoising `input`, both [n, per_image]

@@ -3551,6 +3551,119 @@ int svae_op_fc(const float* x, int b, int k, const float* w, int nout, float* y,
   return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
 }
 
+// ---- recognition heads, latent and split-latent (misc.hip): the engine's launchers with its own strides ----
+static_assert(SVAE_HEADS_FWD_NARROW == HEADS_FWD_NARROW && SVAE_HEADS_FWD_TILE == HEADS_FWD_TILE &&
+              SVAE_HEADS_FWD_SKINNY == HEADS_FWD_SKINNY && SVAE_HEADS_BWD_ROWGROUP == HEADS_BWD_ROWGROUP &&
+              SVAE_HEADS_BWD_PLAIN == HEADS_BWD_PLAIN && SVAE_HEADS_BWD_TILE == HEADS_BWD_TILE,
+              "include/svae_hip.h and kernels.h name the heads kernels alike");
+
+static int op_done() {
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
+}
+
+int svae_op_heads_splits(int k) { return k > 0 ? heads_splits(k) : fail(nullptr, SVAE_EBADARG, "bad op args"); }
+
+int svae_op_heads_fwd(const float* x, int b, int k, const float* wm, const float* ws, int64_t w_gs, int d, float* part,
+                      int nsplit, int pcols, int coff, int groups, int32_t* variant, void* stream) {
+  if (!x || !wm || !ws || !part || b <= 0 || k <= 0 || d <= 0 || d > 32 || groups <= 0 || nsplit <= 0 || pcols <= 0 ||
+      pcols % 2 || coff < 0 || coff + d > pcols / 2 || w_gs < 0)
+    return fail(nullptr, SVAE_EBADARG, "bad op args");
+  if (nsplit < heads_splits(k)) return fail(nullptr, SVAE_EBADARG, "heads_fwd: nsplit < heads_splits(k)");
+  const long long x_gs = (long long)b * k;
+  if (variant) *variant = heads_fwd_path(x, x_gs, k, wm, ws, w_gs, d);
+  heads_fwd(x, x_gs, b, k, wm, ws, w_gs, d, part, (long long)nsplit * b * pcols, pcols, coff, groups,
+            (hipStream_t)stream);
+  return op_done();
+}
+
+int svae_op_latent_fwd(const float* part, int nsplit, int b, int levels, const int32_t* dims, const float* bm,
+                       const float* bs, int bias_gap, float clip, float prior, int uniform, const float* eps,
+                       float* mu, float* sig, float* z, float* kl_img, int groups, void* stream) {
+  if (!part || !dims || !bm || !bs || !eps || !mu || !sig || !z || !kl_img || nsplit <= 0 || b <= 0 || levels <= 0 ||
+      levels > 8 || groups <= 0 || !(prior > 0.f) || bias_gap < 0)
+    return fail(nullptr, SVAE_EBADARG, "bad op args");
+  LatentLvls lv{};
+  lv.L = levels;
+  int Dz = 0;
+  for (int l = 0; l < levels; ++l) {
+    if (dims[l] <= 0 || dims[l] > 256) return fail(nullptr, SVAE_EBADARG, "bad op args");
+    lv.bm[l] = bm + Dz + l * bias_gap;  // a tensor of its own per level, as in the parameter layout
+    lv.bs[l] = bs + Dz + l * bias_gap;
+    lv.off[l] = Dz;
+    lv.dim[l] = dims[l];
+    Dz += dims[l];
+  }
+  if (Dz > 256) return fail(nullptr, SVAE_EBADARG, "latent_fwd: Dz > 256");
+  const long long ms = (long long)b * Dz;
+  latent_fwd(part, (long long)nsplit * b * 2 * Dz, nsplit, b, Dz, lv, Dz + levels * bias_gap, clip, prior, uniform, eps,
+             ms, mu, sig, z, ms, kl_img, b, groups, (hipStream_t)stream);
+  return op_done();
+}
+
+int svae_op_latent_bwd(const float* mu, const float* sig, const float* eps, const float* dz, int b, int dz_dim,
+                       const float* kl_coef, float prior, int uniform, float clip, float* dhead, int groups,
+                       void* stream) {
+  if (!mu || !sig || !eps || !dz || !kl_coef || !dhead || b <= 0 || dz_dim <= 0 || dz_dim > 256 || groups <= 0 ||
+      !(prior > 0.f))
+    return fail(nullptr, SVAE_EBADARG, "bad op args");
+  const long long ms = (long long)b * dz_dim;
+  latent_bwd(mu, sig, eps, dz, ms, ms, b, dz_dim, kl_coef, 1, prior, uniform, clip, dhead, 2 * ms, groups,
+             (hipStream_t)stream);
+  return op_done();
+}
+
+int svae_op_heads_bwd(const float* x, float* dx, int b, int k, const float* wm, const float* ws, int64_t w_gs, int d,
+                      const float* dhead, int dcols, int coff, float* dwm, float* dws, float* dbm, float* dbs,
+                      int accumulate, int groups, int32_t* variant, void* stream) {
+  if (!x || !dx || !wm || !ws || !dhead || !dwm || !dws || !dbm || !dbs || b <= 0 || k <= 0 || d <= 0 || d > 32 ||
+      groups <= 0 || dcols <= 0 || dcols % 2 || coff < 0 || coff + d > dcols / 2 || w_gs < 0)
+    return fail(nullptr, SVAE_EBADARG, "bad op args");
+  if (variant) *variant = heads_bwd_path(b, d);
+  const long long x_gs = (long long)b * k;
+  heads_bwd(x, x_gs, dx, x_gs, b, k, wm, ws, w_gs, d, dhead, (long long)b * dcols, dcols, coff, dwm, dws, dbm, dbs,
+            accumulate != 0, groups, (hipStream_t)stream);
+  return op_done();
+}
+
+int svae_op_splitfc(const float* z, int ldz, int zoff, int b, int k, const float* w, const float* beta, int j, int f,
+                    int ldo, int64_t o_n, float* mean, float* invstd, float* out, int nt, int64_t z_ts, int64_t w_ts,
+                    int64_t bn_ts, int64_t out_ts, void* stream) {
+  if (!z || !w || !beta || !mean || !invstd || !out || b <= 0 || k <= 0 || k > 32 || j <= 0 || f <= 0 || ldo < 0 ||
+      o_n <= 0 || zoff < 0 || ldz < zoff + k || nt <= 0 || nt > SFC_MAXT)
+    return fail(nullptr, SVAE_EBADARG, "bad op args");
+  hipStream_t s = (hipStream_t)stream;
+  if (nt == 1) {
+    splitfc_fwd(z, ldz, zoff, b, k, w, beta, j, mean, invstd, out, o_n, f, ldo, s);
+    return op_done();
+  }
+  SfcSteps a{};
+  for (int i = 0; i < nt; ++i) {
+    a.W[i] = w + i * w_ts;
+    a.beta[i] = beta + i * bn_ts;
+    a.mean[i] = mean + i * bn_ts;
+    a.invstd[i] = invstd + i * bn_ts;
+    a.out[i] = out + i * out_ts;
+    a.o_n[i] = o_n;
+  }
+  splitfc_fwd_steps(z, z_ts, ldz, zoff, b, k, j, f, ldo, 0, a, nt, s);
+  return op_done();
+}
+
+int svae_op_splitfc_bwd(const float* z, int ldz, int zoff, int b, int k, const float* w, const float* beta, int j,
+                        int f, int ldo, int64_t o_n, const float* mean, const float* invstd, const float* dout,
+                        float* dw, float* dbeta, float* dz, void* scratch, int64_t scratch_bytes, void* stream) {
+  if (!z || !w || !beta || !mean || !invstd || !dout || !dw || !dbeta || !dz || !scratch || b <= 0 || k <= 0 ||
+      k > 32 || j <= 0 || f <= 0 || ldo < 0 || o_n <= 0 || zoff < 0 || ldz < zoff + k)
+    return fail(nullptr, SVAE_EBADARG, "bad op args");
+  if ((int64_t)splitfc_blocks(j) * b * k * (int64_t)sizeof(float) > scratch_bytes)
+    return fail(nullptr, SVAE_EBADARG, "scratch too small");
+  hipStream_t s = (hipStream_t)stream;
+  splitfc_bwd(z, ldz, zoff, b, k, w, beta, j, mean, invstd, dout, o_n, f, ldo, dw, dbeta, (float*)scratch, s);
+  splitfc_dz_reduce((const float*)scratch, splitfc_blocks(j), b, k, dz, ldz, zoff, s);
+  return op_done();
+}
+
 // thr(p) = min(floor(p 2^32), 2^32 - 1): a word w < thr(p) with probability p
 static uint32_t prob_threshold(float p) {
   const double t = std::floor((double)p * 4294967296.0);

@@ -248,7 +248,16 @@ int splitfc_blocks(int J);
 
 // ---- recognition heads: [mean|std] = ladder @ [Wm|Ws] (sequential_vae.py:1592-1594,1607-1609) ----
 int heads_splits(int K);
-// part[split][n][coff+o] (mean) and part[split][n][pcols/2+coff+o] (std)
+// which kernel a heads launch takes (= SVAE_HEADS_FWD_* / SVAE_HEADS_BWD_* of include/svae_hip.h): the
+// launchers and the per-op entry points ask the same two host functions
+enum { HEADS_FWD_NARROW = 0, HEADS_FWD_TILE = 1, HEADS_FWD_SKINNY = 2 };
+enum { HEADS_BWD_ROWGROUP = 0, HEADS_BWD_PLAIN = 1, HEADS_BWD_TILE = 2 };
+int heads_fwd_path(const float* X, long long x_gs, int K, const float* Wm, const float* Ws, long long w_gs, int D);
+int heads_bwd_path(int B, int D);
+// part[split][n][coff+o] (mean) and part[split][n][pcols/2+coff+o] (std), for the splits
+// 0 .. heads_splits(K) - 1 only.  Zero-fill contract: latent_fwd sums all nsplit rows of every column, so
+// the rows past a level's own split count (a level with a shorter K than the longest) must hold zeros:
+// the caller clears part before the heads of a step write it.
 void heads_fwd(const float* X, long long x_gs, int B, int K, const float* Wm, const float* Ws, long long w_gs, int D,
                float* part, long long part_gs, int pcols, int coff, int groups, hipStream_t s);
 struct LatentLvls {

@@ -480,12 +480,22 @@ __global__ __launch_bounds__(256) void heads_tile_fwd_kernel(const float* __rest
   }
 }
 
+// the one rule that picks the forward kernel (heads_fwd and svae_op_heads_fwd both ask it)
+int heads_fwd_path(const float* X, long long x_gs, int K, const float* Wm, const float* Ws, long long w_gs, int D) {
+  const bool al = ((uintptr_t)X % 16 == 0) && ((uintptr_t)Wm % 16 == 0) && ((uintptr_t)Ws % 16 == 0) &&
+                  (x_gs % 4 == 0) && (w_gs % 4 == 0);
+  if (D <= 4 && K % 4 == 0 && al) return HEADS_FWD_NARROW;
+  // SVAE_HEADS_TILE bit 0 off: the skinny pass for the wide heads (knob builds read it per call: the A/B tests)
+  const bool tile_off = !(svae_knob("SVAE_HEADS_TILE", 3) & 1);
+  if (D > 4 && D <= 32 && !tile_off) return HEADS_FWD_TILE;
+  return HEADS_FWD_SKINNY;
+}
+
 void heads_fwd(const float* X, long long x_gs, int B, int K, const float* Wm, const float* Ws, long long w_gs, int D,
                float* part, long long part_gs, int pcols, int coff, int groups, hipStream_t s) {
   // mean and stddev heads in one pass over X (the shared recognition features)
-  const bool al = ((uintptr_t)X % 16 == 0) && ((uintptr_t)Wm % 16 == 0) && ((uintptr_t)Ws % 16 == 0) &&
-                  (x_gs % 4 == 0) && (w_gs % 4 == 0);
-  if (D <= 4 && K % 4 == 0 && al) {
+  const int path = heads_fwd_path(X, x_gs, K, Wm, Ws, w_gs, D);
+  if (path == HEADS_FWD_NARROW) {
     dim3 grid((B + HF_ROWS - 1) / HF_ROWS, heads_splits(K), groups);
     const int c2 = pcols / 2 + coff;
 #define HF_L(DD) hipLaunchKernelGGL(heads_fwd_kernel<DD>, grid, dim3(256), 0, s, X, x_gs, B, K, Wm, Ws, w_gs, part, \
@@ -497,9 +507,7 @@ void heads_fwd(const float* X, long long x_gs, int B, int K, const float* Wm, co
 #undef HF_L
     return;
   }
-  // SVAE_HEADS_TILE bit 0 off: the skinny pass for the wide heads (knob builds read it per call: the A/B tests)
-  const bool tile_off = !(svae_knob("SVAE_HEADS_TILE", 3) & 1);
-  if (D > 4 && D <= 32 && !tile_off) {
+  if (path == HEADS_FWD_TILE) {
     dim3 grid((B + 63) / 64, heads_splits(K), groups);
     hipLaunchKernelGGL(heads_tile_fwd_kernel, grid, dim3(256), 0, s, X, x_gs, B, K, Wm, Ws, w_gs, D, part, part_gs, pcols,
                        coff, pcols / 2 + coff);
@@ -892,20 +900,28 @@ __global__ __launch_bounds__(256) void heads_tile_bwd_kernel(const float* __rest
   }
 }
 
+// the one rule that picks the backward kernel (heads_bwd and svae_op_heads_bwd both ask it)
+int heads_bwd_path(int B, int D) {
+  // SVAE_HEADS_TILE bit 1 off: heads_bwd_kernel<32> for the wide heads (knob builds: per call)
+  const bool tile_off = !(svae_knob("SVAE_HEADS_TILE", 3) & 2);
+  if (D > 8 && D <= 32 && !tile_off) return HEADS_BWD_TILE;
+  // SVAE_HEADS_RG=0: one thread per k over all rows (round 3; knob builds: per call)
+  const bool rg_on = svae_knob("SVAE_HEADS_RG", 1) != 0;
+  if (rg_on && B % (HR_RG * 8) == 0 && D <= 8) return HEADS_BWD_ROWGROUP;
+  return HEADS_BWD_PLAIN;
+}
+
 void heads_bwd(const float* X, long long x_gs, float* dX, long long dx_gs, int B, int K, const float* Wm,
                const float* Ws, long long w_gs, int D, const float* dhead, long long dh_gs, int dcols, int coff,
                float* dWm, float* dWs, float* dbm, float* dbs, int accumulate, int groups, hipStream_t s) {
-  // SVAE_HEADS_TILE bit 1 off: heads_bwd_kernel<32> for the wide heads (knob builds: per call)
-  const bool tile_off = !(svae_knob("SVAE_HEADS_TILE", 3) & 2);
-  if (D > 8 && D <= 32 && !tile_off) {
+  const int path = heads_bwd_path(B, D);
+  if (path == HEADS_BWD_TILE) {
     dim3 grid((K + 63) / 64, groups);
     hipLaunchKernelGGL(heads_tile_bwd_kernel, grid, dim3(256), 0, s, X, x_gs, dX, dx_gs, B, K, Wm, Ws, w_gs, D, dhead,
                        dh_gs, dcols, coff, dWm, dWs, dbm, dbs, accumulate);
     return;
   }
-  // SVAE_HEADS_RG=0: one thread per k over all rows (round 3; knob builds: per call)
-  const bool rg_on = svae_knob("SVAE_HEADS_RG", 1) != 0;
-  if (rg_on && B % (HR_RG * 8) == 0 && D <= 8) {
+  if (path == HEADS_BWD_ROWGROUP) {
     dim3 grid((K + 63) / 64, groups);
     size_t lds = (size_t)B * 2 * D * sizeof(float) + (size_t)2 * 8 * HR_RG * 64 * sizeof(float);
     if (D <= 4)
