@@ -340,6 +340,41 @@ int svae_op_make_batch(const void* data, int data_u8, const int32_t* idx, int64_
                        float lo, float hi, float pepper_prob, float salt_prob, float gaussian_scale, uint64_t seed,
                        uint64_t offset, float* target, float* input, void* stream);
 
+/* Segmented statistics of one fp32 device array in one pass (no reference counterpart; the numbers behind
+ * the training summaries).  Segments (offset, length) in elements of x: disjoint, ascending, gaps allowed,
+ * any alignment, length 0 legal.  With y = clamp(x, -c, +c) (c = +inf: none), row s of out [n_seg][8] (fp64):
+ *   col 0  number of finite elements
+ *   col 1  sum y
+ *   col 2  sum |y|
+ *   col 3  sum y^2
+ *   col 4  max |x| over the finite elements (0 if none)
+ *   col 5  number of finite elements with |x| > c
+ *   col 6  number of non-finite elements (NaN, +-inf)
+ *   col 7  0 (reserved)
+ * A non-finite element is counted in col 6 and contributes to nothing else.  Sums are accumulated in fp64 in
+ * a fixed order (csrc/stats.hip): the result depends on x, the segments and c only, two calls give the same
+ * bytes, and nothing outside a segment is read.
+ *
+ * The plan is built on the host (no GPU needed) and uploaded once per (array, segmentation).  It cuts segment
+ * s at the element indices (offset_s & ~3) + k * SVAE_STATS_CHUNK, so no chunk crosses a segment or exceeds
+ * SVAE_STATS_CHUNK elements.  Layout, in int64 words:
+ *   table[s], s = 0 .. n_seg      index of segment s's first chunk; table[n_seg] = n_chunks
+ *   table[n_seg + 1 + 2 k]        first element of chunk k
+ *   table[n_seg + 2 + 2 k]        (segment of chunk k) << 32 | its length
+ * so a table holds n_seg + 1 + 2 * n_chunks words.  The plan call returns n_chunks (>= 0); table == NULL only
+ * counts.  SVAE_EBADARG: a null array with n_seg > 0, a negative count, offset or length, segments out of order or
+ * overlapping, or cap_words (the words table can hold) too small -- the message names both sizes. */
+#define SVAE_STATS_CHUNK 16384
+int64_t svae_op_stats_plan(const int64_t* offsets, const int64_t* lengths, int32_t n_seg, int64_t* table,
+                           int64_t cap_words);
+/* The launch: plan is the table in device memory, partials a device scratch of max(1, n_chunks) * 8 doubles, out
+ * n_seg * 8 doubles (rows past n_seg are not touched).  At most two kernel launches on `stream`, no allocation,
+ * no synchronisation; 16-byte loads when x is 16-byte aligned, the same sums in the same order when it is not.
+ * n_seg and n_chunks must be the plan's (the device cannot check them).  SVAE_EBADARG: a null pointer, a
+ * negative count, c < 0 or NaN. */
+int svae_op_tensor_stats(const float* x, const int64_t* plan, int32_t n_seg, int64_t n_chunks, float c,
+                         double* partials, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3699,4 +3699,30 @@ int svae_op_make_batch(const void* data, int data_u8, const int32_t* idx, int64_
   return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
 }
 
+int64_t svae_op_stats_plan(const int64_t* offsets, const int64_t* lengths, int32_t n_seg, int64_t* table,
+                           int64_t cap_words) {
+  if (n_seg < 0 || (n_seg > 0 && (!offsets || !lengths)) || cap_words < 0)
+    return fail(nullptr, SVAE_EBADARG, "stats_plan: null segments or a negative count");
+  const long long n = stats_plan((const long long*)offsets, (const long long*)lengths, n_seg, (long long*)table,
+                                 cap_words);
+  if (n == -1)
+    return fail(nullptr, SVAE_EBADARG, "stats_plan: segments must be non-negative, ascending and disjoint");
+  if (n == -2) {
+    const long long nc = stats_plan((const long long*)offsets, (const long long*)lengths, n_seg, nullptr, 0);
+    return fail(nullptr, SVAE_EBADARG, "stats_plan: the table holds " + std::to_string((long long)cap_words) +
+                                           " words, the plan needs " + std::to_string(stats_plan_words(n_seg, nc)));
+  }
+  return n;
+}
+
+int svae_op_tensor_stats(const float* x, const int64_t* plan, int32_t n_seg, int64_t n_chunks, float c,
+                         double* partials, double* out, void* stream) {
+  if (!x || !plan || !partials || !out) return fail(nullptr, SVAE_EBADARG, "tensor_stats: null pointer");
+  if (n_seg < 0 || n_chunks < 0) return fail(nullptr, SVAE_EBADARG, "tensor_stats: negative count");
+  if (!(c >= 0.f)) return fail(nullptr, SVAE_EBADARG, "tensor_stats: the clamp must be >= 0 (+inf: none)");
+  tensor_stats(x, (const long long*)plan, n_seg, n_chunks, c, partials, out, (hipStream_t)stream);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
+}
+
 }  // extern "C"

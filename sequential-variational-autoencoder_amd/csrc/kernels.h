@@ -350,6 +350,16 @@ struct MakeBatchArgs {
   float* target; float* input;       // either may be nullptr
 };
 void make_batch(const MakeBatchArgs& a, hipStream_t s);
+// ---- segmented statistics (stats.hip): the eight fp64 columns of svae_op_tensor_stats per segment ----
+// plan table (int64 words): [0, n_seg] the index of every segment's first chunk (entry n_seg = n_chunks), then
+// per chunk (begin, segment << 32 | length).  stats_plan returns the chunk count (table == nullptr: count only),
+// -1 for a negative, unordered or overlapping segment, -2 when cap_words < stats_plan_words().
+inline long long stats_plan_words(int n_seg, long long n_chunks) { return (long long)n_seg + 1 + 2 * n_chunks; }
+long long stats_plan(const long long* offsets, const long long* lengths, int n_seg, long long* table,
+                     long long cap_words);
+// part: n_chunks * 8 doubles; out: n_seg * 8 doubles; at most two launches on s
+void tensor_stats(const float* x, const long long* plan, int n_seg, long long n_chunks, float c, double* part,
+                  double* out, hipStream_t s);
 // column sums of X [rows][C<=4] -> out0[0..n0), out1[0..C-n0)   (part: scratch >= 1024 floats)
 void colsum_small(const float* X, int ld, long long rows, int C, float* part, float* out0, int n0, float* out1,
                   hipStream_t s);

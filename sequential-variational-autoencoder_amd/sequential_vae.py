@@ -60,6 +60,8 @@ class SequentialVAE:
         self.ctx = h
         _lib.check(self.L.svae_bind(self.ctx, _lib.ptr(self.params), _lib.ptr(self.grads)), self.ctx)
         self._last_reg = 1.0
+        self._forwarded = False   # a training forward has run (and no generate since): summaries() may read it
+        self._summaries = None    # summaries.Summaries: plans and device buffers, built at the first call
         # Adam updates applied so far (the AdamOptimizer's step count behind beta1_power); with the
         # improvement-maximisation loss two apply_gradients run per iteration (:1267, :1306)
         self.adam_updates = 0
@@ -120,6 +122,7 @@ class SequentialVAE:
         self._last_reg = float(reg_coeff)
         _lib.check(self.L.svae_forward(self.ctx, _lib.ptr(x), _lib.ptr(target), _lib.ptr(e), float(reg_coeff),
                                        _lib.stream_ptr(stream)), self.ctx)
+        self._forwarded = True
 
     def backward(self, stream=None):
         s = stream if stream is not None else torch.cuda.current_stream(self.device)
@@ -255,6 +258,21 @@ class SequentialVAE:
 
     def latent(self, which, t):
         return self.copy_out(which, t, self.cfg.batch * self.cfg.latent_dim).view(self.cfg.batch, self.cfg.latent_dim)
+
+    def summaries(self, lr=None):
+        """The reference's training summaries (summaries.summary_names(cfg), in that order) as {name: float}
+        from device state as it stands: the last forward's loss terms and latents, the bound gradient buffers
+        as they are, the parameters as they are (after train(): the updated weights and the gradients that
+        produced the update).  No forward runs, so no Philox counter moves and training is bit for bit what it
+        is without the call.  Update ratios are lr * grads_norm / weights_norm (:1288), lr defaulting to
+        ``learning_rate``.  Plans and device buffers are built at the first call and kept; one device -> host
+        copy per call."""
+        if not self._forwarded:
+            raise RuntimeError("summaries() describes the last forward: run forward() or train() first")
+        if self._summaries is None:
+            from .summaries import Summaries
+            self._summaries = Summaries(self)
+        return self._summaries(self, self.learning_rate if lr is None else float(lr))
 
     def param_dict(self):
         return unflatten(self.params.cpu().numpy(), self.table)
@@ -397,6 +415,7 @@ class SequentialVAE:
             nz = self._dev(noise)
             _lib.check(self.L.svae_set_chain_noise(self.ctx, _lib.ptr(nz)), self.ctx)
         self._keep = (e, nz)
+        self._forwarded = False  # svae_generate invalidates the training forward state summaries() reads
         _lib.check(self.L.svae_generate(self.ctx, _lib.ptr(e), _lib.stream_ptr(stream)), self.ctx)
         return [self.xhat(t) for t in range(self.cfg.mc_steps)]
 

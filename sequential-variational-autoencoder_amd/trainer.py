@@ -33,7 +33,7 @@ class NoisyTrainer:
     test_seed_xor = 0x7E577E57A5A5A5A5  # test-noise key = seed ^ this
 
     def __init__(self, network, dataset, denoise_train=False, vis_frequency=1000, plot_reconstruction=False,
-                 base_dir=None, logger=None, seed=0):
+                 base_dir=None, logger=None, seed=0, summary_freq=0):
         if list(dataset.data_dims) != list(network.data_dims):
             raise ValueError("dataset images %s, network %s" % (dataset.data_dims, network.data_dims))
         if tuple(dataset.range) != tuple(float(v) for v in network.cfg.range):
@@ -47,6 +47,9 @@ class NoisyTrainer:
         self.plot_reconstruction_enabled = bool(plot_reconstruction)
         self.base_dir = base_dir
         self.LOG = logger if logger is not None else logging.getLogger("svae.trainer")
+        # every summary_freq-th step appends network.summaries() to <base_dir>/summaries.jsonl (the reference's
+        # tb_summary_freq is 10); 0: none, and the step is exactly what it is without this option
+        self.summary_freq = int(summary_freq)
         self.batch_size = network.batch_size
         self.data_dims = list(dataset.data_dims)
         self.device = network.device
@@ -110,7 +113,23 @@ class NoisyTrainer:
         inp, tgt = self._next()
         loss = self.network.train(inp, tgt)
         self.iteration += 1
+        if self.summary_freq > 0 and self.iteration % self.summary_freq == 0:
+            self.write_summaries()
         return loss
+
+    def write_summaries(self):
+        """One line {"iteration", "learning_rate", "reg_coeff", <network.summaries()>}: logged at debug level
+        and, with a base_dir, appended to <base_dir>/summaries.jsonl (a resumed run goes on in the same file)."""
+        net = self.network
+        row = {"iteration": self.iteration, "learning_rate": net.learning_rate, "reg_coeff": net._last_reg}
+        row.update(net.summaries())
+        line = json.dumps(row)
+        self.LOG.debug(line)
+        if self.base_dir is not None:
+            os.makedirs(self.base_dir, exist_ok=True)
+            with open(os.path.join(self.base_dir, "summaries.jsonl"), "a") as f:
+                f.write(line + "\n")
+        return row
 
     def train(self, num_iters=None):
         """trainer.py:82-109: every vis_frequency iterations test + visualise, every log_loss_freq log,

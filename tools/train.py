@@ -31,6 +31,9 @@ def parse(argv=None):
     ap.add_argument("--denoise_train", action="store_true", help="add salt-and-pepper and Gaussian noise to the input")
     ap.add_argument("--plot_reconstruction", action="store_true")
     ap.add_argument("--vis_frequency", type=int, default=1000, help="training batches per test + visualisation")
+    ap.add_argument("--summary_freq", type=int, default=0,
+                    help="append the training summaries to <model dir>/summaries.jsonl every N iterations "
+                         "(0: off; the reference's tb_summary_freq is 10)")
     ap.add_argument("--iters", type=int, default=None, help="iterations to run (default: the reference's 10^7)")
     ap.add_argument("--dtype", default="bf16x6", choices=["fp32", "bf16", "bf16x6"])
     ap.add_argument("--models_dir", default="models")
@@ -77,7 +80,8 @@ def main(argv=None):
     net = SV(cfg, seed=a.seed)
     net.name = a.netname
     trainer = NT(net, ds, denoise_train=a.denoise_train, vis_frequency=a.vis_frequency,
-                 plot_reconstruction=a.plot_reconstruction, base_dir=base_dir, logger=log, seed=a.seed)
+                 plot_reconstruction=a.plot_reconstruction, base_dir=base_dir, logger=log, seed=a.seed,
+                 summary_freq=a.summary_freq)
     if a.continue_training and os.path.exists(os.path.join(base_dir, "trainer.json")):
         trainer.load(base_dir)
         log.info("resumed at iteration %d" % trainer.iteration)
