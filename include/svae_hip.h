@@ -235,9 +235,24 @@ int svae_op_gather_bf16(const float* x, int n, int h, int cin, const void* w_nk,
  * ([4,4,cin,cout] / [4,4,cout,cin]) from fp32 NHWC x and dy, operands rounded to bf16, fp32
  * accumulation.  path: 0 tap-merged weight-GEMM kernel, 2 halo weight-GEMM where it qualifies;
  * + 16: x is a bf16 tensor, + 32: dy is a bf16 tensor (the engine's bf16 activation / BN-backward
- * storage, opload.h).  scratch: split slab (required). */
+ * storage, opload.h).  + 32 is ignored for a layer whose input gradient takes the fp32 small-N gather, as the
+ * engine keeps that layer's dy in fp32: cin % 4 != 0, unless it is a conv with cout % 32 == 0.
+ * + 64: the split mode (dtype bf16x6): fp32 x and dy, each staged as two bf16 planes, three plane products
+ * per pair (opload.h split8 / mfma_split<2>); SVAE_EBADARG together with + 16 or + 32.
+ * scratch: split slab (required). */
 int svae_op_wgrad_bf16(const float* x, int n, int h, int cin, const float* dy, int cout, int stride, int transpose,
                        int path, float* dw, void* scratch, int64_t scratch_bytes, void* stream);
+/* kernel the last svae_op_wgrad_bf16 call of this process launched, as the engine's dispatch recorded it
+ * (pure host; SVAE_WGRAD_NONE before the first call or after one that failed before its launch) */
+enum {
+  SVAE_WGRAD_NONE = 0,
+  SVAE_WGRAD_TAP_MERGED = 1, /* wgrad_bf16_kernel, taps merged into M */
+  SVAE_WGRAD_HALO = 2,       /* wgrad_halo_kernel, run-time geometry (bf16 mode only) */
+  SVAE_WGRAD_HALO2 = 3,      /* wgrad_halo2_kernel, compile-time geometry */
+  SVAE_WGRAD_SMALLC = 4,     /* wgrad_smallc_kernel, <= 4 image channels */
+  SVAE_WGRAD_FP32 = 5        /* the fp32 weight-GEMM (never from svae_op_wgrad_bf16) */
+};
+int svae_op_wgrad_last_kernel(void);
 int svae_op_conv_dgrad(const float* dy, int n, int h, int cin, const float* w, int cout, int stride, int transpose,
                        float* dx, void* stream);
 int svae_op_conv_wgrad(const float* x, int n, int h, int cin, const float* dy, int cout, int stride, int transpose,
@@ -266,6 +281,27 @@ int svae_op_bn_act_bwd(const float* dy, const float* y, const float* x, int64_t 
                        void* stream);
 /* y[B,N] = x[B,K] @ w[K,N]  (fully_connected, no bias) */
 int svae_op_fc(const float* x, int b, int k, const float* w, int nout, float* y, void* stream);
+/* FC GEMM of the bf16 and split modes: y[b][nout] = x[b][k] . w_nk[nout][k]^T through the engine's bf16
+ * dispatch on a dense launch.  The FC forward (weights [out][in]) and the FC input gradient (weights
+ * [in][out] read as n = in, k = out) are this launch at different shapes.  x fp32, rounded to bf16 while
+ * staged; w_nk bf16.  path: 2 the engine's choice (dense_kw where it qualifies, else the tiled per-tap
+ * kernel), 0 the tiled per-tap kernel.
+ *   + 16: the split mode on three bf16 planes: w_nk holds three planes nout*k elements apart, fp32 x split
+ *         in registers, six plane products
+ *   + 32 (with + 16): two scaled fp16 planes fp16(w * 2^10), fp16(w * 2^10 - h0) follow the three; x takes
+ *         a per-wave running exponent, three fp16 products
+ *   + 64: x is a bf16 tensor (bf16 mode only: SVAE_EBADARG with + 16)
+ * scratch (optional, NULL: no grid split): the split-K slabs.  *variant (may be NULL) reports the kernel.
+ * No allocation, no synchronisation.  SVAE_EBADARG: k % 4 or nout % 4, + 32 without + 16, or a split
+ * launch (+ 16) that has no split kernel (path 0, k % 16, nout % 32). */
+enum { SVAE_DENSE_TILED = 0, SVAE_DENSE_KW = 1, SVAE_DENSE_KW_SPLITK = 2 };
+int svae_op_dense_bf16(const void* x, int b, int k, const void* w_nk, int nout, int path, float* y, void* scratch,
+                       int64_t scratch_bytes, int32_t* variant, void* stream);
+/* FC weight gradient dw[k][nout] = x[b][k]^T . dy[b][nout] through the engine's weight-GEMM dispatch, set up
+ * as the FC backward does (one tap, one split over the batch rows).  mode 0: fp32; 1: bf16 (operands rounded
+ * while staged; + 16: x is a bf16 tensor, + 32: dy is a bf16 tensor); 2: the split mode (fp32 operands as
+ * three bf16 planes, six plane products).  nout % 4 == 0.  No allocation, no synchronisation. */
+int svae_op_fc_wgrad(const void* x, int b, int k, const void* dy, int nout, int mode, float* dw, void* stream);
 /* ---- recognition heads, latent and split-latent kernels (csrc/misc.hip), each through the engine's own
  * launcher.  Device pointers unless said otherwise, the caller's stream, no allocation.  SVAE_EBADARG: a
  * null pointer, a non-positive size, d > 32 (heads), Dz > 256 (latent), k > 32 (split-latent), or what

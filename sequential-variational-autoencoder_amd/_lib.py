@@ -131,6 +131,9 @@ def _load(path):
         "svae_op_flat_wgrad": ([vp, i32, i32, i32, vp, i32, vp, vp, i64, vp], i32),
         "svae_op_gather_bf16": ([vp, i32, i32, i32, vp, i32, i32, i32, i32, vp, vp, i64, vp], i32),
         "svae_op_wgrad_bf16": ([vp, i32, i32, i32, vp, i32, i32, i32, i32, vp, vp, i64, vp], i32),
+        "svae_op_wgrad_last_kernel": ([], i32),
+        "svae_op_dense_bf16": ([vp, i32, i32, vp, i32, i32, vp, vp, i64, ctypes.POINTER(i32), vp], i32),
+        "svae_op_fc_wgrad": ([vp, i32, i32, vp, i32, i32, vp, vp], i32),
         "svae_op_make_batch": ([vp, i32, vp, i64, i32, i64, f32, f32, f32, f32, f32, u64, u64, vp, vp, vp], i32),
         "svae_op_stats_plan": ([ctypes.POINTER(i64), ctypes.POINTER(i64), i32, ctypes.POINTER(i64), i64], i64),
         "svae_op_tensor_stats": ([vp, vp, i32, i64, f32, vp, vp, vp], i32),
@@ -221,7 +224,8 @@ EXPORTED = ["svae_param_count", "svae_param_layout", "svae_create", "svae_destro
             "svae_set_external_grads", "svae_build_hash", "svae_op_flat_conv", "svae_op_flat_dgrad",
             "svae_op_flat_wgrad", "svae_op_make_batch", "svae_op_heads_splits", "svae_op_heads_fwd",
             "svae_op_latent_fwd", "svae_op_latent_bwd", "svae_op_heads_bwd", "svae_op_splitfc",
-            "svae_op_splitfc_bwd", "svae_op_stats_plan", "svae_op_tensor_stats"]
+            "svae_op_splitfc_bwd", "svae_op_stats_plan", "svae_op_tensor_stats", "svae_op_wgrad_last_kernel",
+            "svae_op_dense_bf16", "svae_op_fc_wgrad"]
 # include/svae_pcnn.h (the PixelCNN++ head)
 PCNN_EXPORTED = ["svae_pcnn_wnorm", "svae_pcnn_wnorm_bwd", "svae_pcnn_conv", "svae_pcnn_conv_wgrad", "svae_pcnn_colsum",
                  "svae_pcnn_colsum_absmax", "svae_pcnn_im2col_h16", "svae_pcnn_conv_planes_amax",

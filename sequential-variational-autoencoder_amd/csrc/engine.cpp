@@ -667,6 +667,7 @@ struct svae_ctx {
   // bf16 mode: BN-backward outputs (dpre) stored as bf16 -- their only consumers, the dgrad and
   // wgrad GEMMs, round them identically while staging (opload.h)
   int dbf = 0;
+  int wg_last = 0;  // kernel of the last conv_wgrad dispatch (SVAE_WGRAD_*; read by svae_op_wgrad_last_kernel)
   int abf = 0;  // bf16 mode: the post-activation tensors read only by bf16 GEMMs are stored as bf16
   // bf16 mode: every conv layer's pre-BN output is stored as bf16 by its GEMM epilogue (the BN statistics
   // of the stored values); the BN apply / backward passes and the fused backward-BN epilogues widen it
@@ -1248,8 +1249,10 @@ static int conv_wgrad(svae_ctx* c, const ConvL& L, int groups, long long w_gs, V
     // the T-batched recognition layers (groups > 1) run after the chain backward, beside the recognition
     // input gradients and then alone: twice the default split target (SVAE_WH2_GTARGET, 0 = the default)
     static const int gtarget = svae_knob("SVAE_WH2_GTARGET", 256);
-    if (wgrad_halo2(w, groups, c->slab, c->slab_cap, dW, w_gs, c->st, ev ? ev[1] : nullptr, groups > 1 ? gtarget : 0))
+    if (wgrad_halo2(w, groups, c->slab, c->slab_cap, dW, w_gs, c->st, ev ? ev[1] : nullptr, groups > 1 ? gtarget : 0)) {
+      c->wg_last = SVAE_WGRAD_HALO2;
       return 0;
+    }
   }
   const bool bfk = c->m.g.bf16 && !c->m.g.split;  // plain-bf16 weight-GEMM kernels
   if (bfk && c->wg_path != 0 && wgrad_halo_enabled()) {
@@ -1277,13 +1280,18 @@ static int conv_wgrad(svae_ctx* c, const ConvL& L, int groups, long long w_gs, V
         ev = probe_pair(c, w.g.stride == 1 ? KID_WHALO_32_S1 : KID_WHALO_32_S2,
                         2.0 * 16 * (double)w.M * w.N * w.rows * groups);
       wgrad_halo(pl, w, groups, c->st, ev ? ev[1] : nullptr);
+      c->wg_last = SVAE_WGRAD_HALO;
       if (w.nsplit > 1)
         wgrad_reduce(c->slab, w.p_gs, w.nsplit, 16, w.M, w.N, dW, w_gs, w.M, nullptr, 0, 0, groups, c->st);
       return 0;
     }
   }
   // image-space stride-2 conv with Cin <= 3: im2col in LDS, MFMA over pixel chunks
-  if ((bfk || c->m.g.split) && wgrad_smallc(w, groups, c->slab, c->slab_cap, dW, w_gs, c->st)) return 0;
+  if ((bfk || c->m.g.split) && wgrad_smallc(w, groups, c->slab, c->slab_cap, dW, w_gs, c->st)) {
+    c->wg_last = SVAE_WGRAD_SMALLC;
+    return 0;
+  }
+  c->wg_last = (bfk || c->m.g.split) ? SVAE_WGRAD_TAP_MERGED : SVAE_WGRAD_FP32;
   if (bfk || c->m.g.split)  // tap-merged tiles; longer splits (less slab traffic)
     choose_split(w.rows, 1, wgrad_bf16_tiles(w), groups, 16LL * w.M * w.N, c->slab_cap, w.nsplit, w.chunk, 2048,
                  256);
@@ -3391,17 +3399,27 @@ int svae_op_gather_bf16(const float* x, int n, int h, int cin, const void* w_nk,
   return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
 }
 
+// the context svae_op_wgrad_bf16 runs conv_wgrad on (process-wide: a test entry point, one caller at a time)
+static svae_ctx& wgrad_op_ctx() {
+  static svae_ctx dummy;
+  return dummy;
+}
+
 int svae_op_wgrad_bf16(const float* x, int n, int h, int cin, const float* dy, int cout, int stride, int transpose,
                        int path, float* dw, void* scratch, int64_t scratch_bytes, void* stream) {
   const int xbf = (path >> 4) & 1, dybf = (path >> 5) & 1;  // operand storage bits (bf16 tensors)
+  const int split = (path >> 6) & 1;                        // bit 6: the split mode (fp32 operands, two planes)
+  if (path < 0 || (path & ~0x7f) || (split && (xbf || dybf))) return fail(nullptr, SVAE_EBADARG, "bad op args");
   path &= 15;
   if (!x || !dy || !dw || !scratch || (path != 0 && path != 2 && path != 3))
     return fail(nullptr, SVAE_EBADARG, "bad op args");
-  static svae_ctx dummy;
+  svae_ctx& dummy = wgrad_op_ctx();
   dummy.m.g.B = n;
   dummy.m.g.bf16 = 1;
+  dummy.m.g.split = split;
   dummy.dbf = dybf;
   dummy.wg_path = path;
+  dummy.wg_last = SVAE_WGRAD_NONE;
   dummy.st = (hipStream_t)stream;
   dummy.slab = (float*)scratch;
   dummy.slab_cap = scratch_bytes / (int64_t)sizeof(float);
@@ -3410,11 +3428,14 @@ int svae_op_wgrad_bf16(const float* x, int n, int h, int cin, const float* dy, i
   L.hout = L.tr ? h * stride : h / stride;
   const int r = conv_wgrad(&dummy, L, 1, 0, View{(float*)x, cin, 0, xbf}, dy, 0, dw);
   dummy.m.g.bf16 = 0;
+  dummy.m.g.split = 0;
   dummy.dbf = 0;
   if (r) return fail(nullptr, r, dummy.err);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
 }
+
+int svae_op_wgrad_last_kernel(void) { return wgrad_op_ctx().wg_last; }
 
 int svae_op_conv_dgrad(const float* dy, int n, int h, int cin, const float* w, int cout, int stride, int transpose,
                        float* dx, void* stream) {
@@ -3560,6 +3581,64 @@ static_assert(SVAE_HEADS_FWD_NARROW == HEADS_FWD_NARROW && SVAE_HEADS_FWD_TILE =
 static int op_done() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
+}
+
+int svae_op_dense_bf16(const void* x, int b, int k, const void* w_nk, int nout, int path, float* y, void* scratch,
+                       int64_t scratch_bytes, int32_t* variant, void* stream) {
+  const int planes = (path >> 4) & 1, h16 = (path >> 5) & 1, xbf = (path >> 6) & 1;
+  const int p = path & 15;
+  if (!x || !w_nk || !y || b <= 0 || k <= 0 || nout <= 0 || k % 4 || nout % 4 || path < 0 || (path & ~0x7f) ||
+      (p != 0 && p != 2) || (h16 && !planes) || (xbf && planes) || scratch_bytes < 0)
+    return fail(nullptr, SVAE_EBADARG, "bad op args");
+  FwdArgs a{};  // as fc_bn_fwd / fc_bn_bwd build theirs: weights [n][k], one row per batch element
+  a.A = (const float*)x; a.lda = k; a.a_bf16 = xbf;
+  a.Bh = w_nk; a.b_nk = 1; a.ldb = k; a.b_tap = 0;
+  a.C = y; a.ldc = nout;
+  a.N = nout; a.Cin = k;
+  a.g.mode = GM_DENSE; a.g.nimg = b; a.g.ksz = 1; a.g.stride = 1;
+  a.rows = b; a.nclass = 1;
+  a.part = (float*)scratch;
+  a.part_cap = scratch ? scratch_bytes / (int64_t)sizeof(float) : 0;
+  if (planes) {
+    a.nsp = 3;
+    a.b_plane = (long long)nout * k;
+    a.h16 = h16;
+    // the split planes exist in dense_kw alone (the tiled kernel has no split form)
+    if (p != 2 || !dense_kw_ok(a, 1)) return fail(nullptr, SVAE_EBADARG, "no split kernel for this dense launch");
+  }
+  if (variant)
+    *variant = (p == 2 && dense_kw_ok(a, 1)) ? (dense_kw_ks(a) > 1 ? SVAE_DENSE_KW_SPLITK : SVAE_DENSE_KW) : SVAE_DENSE_TILED;
+  if (igemm_bf16_path(a, 1, p, (hipStream_t)stream) < 0)
+    return fail(nullptr, SVAE_EBADARG, "no split kernel for this dense launch");
+  return op_done();
+}
+
+int svae_op_fc_wgrad(const void* x, int b, int k, const void* dy, int nout, int mode, float* dw, void* stream) {
+  const int xbf = (mode >> 4) & 1, dybf = (mode >> 5) & 1;
+  const int m = mode & 15;
+  if (!x || !dy || !dw || b <= 0 || k <= 0 || nout <= 0 || nout % 4 || mode < 0 || (mode & ~0x3f) || m > 2 ||
+      ((xbf || dybf) && m != 1) || (xbf && k % 4))
+    return fail(nullptr, SVAE_EBADARG, "bad op args");
+  static svae_ctx dummy;
+  dummy.m.g.B = b;
+  dummy.m.g.bf16 = m != 0;
+  dummy.m.g.split = m == 2;
+  dummy.st = (hipStream_t)stream;
+  WgArgs w{};  // fc_bn_bwd's weight-GEMM: one split over the batch rows, dW [k][nout] written directly
+  w.G = (const float*)x; w.ldg = k; w.g_bf16 = xbf;
+  w.D = (const float*)dy; w.ldd = nout; w.d_bf16 = dybf;
+  w.M = k; w.N = nout;
+  w.g.mode = GM_DENSE; w.g.nimg = b; w.g.ksz = 1; w.g.stride = 1;
+  w.ntap = 1;
+  w.rows = b;
+  w.nsplit = 1;
+  w.chunk = (b + 31) / 32 * 32;
+  w.part = dw;
+  w.nsp = m == 2 ? 3 : 1;
+  wgemm(&dummy, w, 1);
+  dummy.m.g.bf16 = 0;
+  dummy.m.g.split = 0;
+  return op_done();
 }
 
 int svae_op_heads_splits(int k) { return k > 0 ? heads_splits(k) : fail(nullptr, SVAE_EBADARG, "bad op args"); }
