@@ -411,6 +411,34 @@ int64_t svae_op_stats_plan(const int64_t* offsets, const int64_t* lengths, int32
 int svae_op_tensor_stats(const float* x, const int64_t* plan, int32_t n_seg, int64_t n_chunks, float c,
                          double* partials, double* out, void* stream);
 
+/* Per-image quality metrics in one launch on `stream` (no allocation, no synchronisation; no reference
+ * counterpart: the numbers behind NoisyTrainer.evaluate).  x [n, h, w, c] and y [ny, h, w, c] are fp32 NHWC on
+ * the device; image i of x is compared with image i % ny of y, so one call scores a stack of k * ny images
+ * against ny targets.  Row i of out [n][4] (fp64; rows past n are not touched):
+ *   col 0  sum (x - y)^2 over the h * w * c elements
+ *   col 1  sum |x - y|
+ *   col 2  mean SSIM over the (h - 10) * (w - 10) valid window positions and the c channels
+ *   col 3  number of non-finite elements (NaN, +-inf) among the two images
+ * SSIM is Wang et al. 2004: per channel, an SVAE_SSIM_WINDOW^2 Gaussian window w of standard deviation
+ * SVAE_SSIM_SIGMA normalised to sum 1 (the outer product of the normalised 1-D window with itself), weighted
+ * population statistics mu = sum w x, var = sum w x^2 - mu^2, cov = sum w x y - mu_x mu_y, and
+ *   SSIM = (2 mu_x mu_y + C1) (2 cov + C2) / ((mu_x^2 + mu_y^2 + C1) (var_x + var_y + C2)),
+ * C1 = (SVAE_SSIM_K1 L)^2, C2 = (SVAE_SSIM_K2 L)^2, L = data_range; only window positions that lie wholly
+ * inside the image count.  All arithmetic after the load is fp64, in a fixed order without atomics
+ * (csrc/metrics.hip): row i depends on image i and its reference only (not on n, the grid or an address) and
+ * two calls give the same bytes.  16-byte loads where both images are 16-byte aligned, the same values in the
+ * same order where not.  A non-finite element is counted in col 3; cols 0 .. 2 of that row then follow IEEE
+ * arithmetic (NaN or inf), other rows are not affected.  The kernel walks the valid positions in tiles of
+ * SVAE_METRICS_TILE x SVAE_METRICS_TILE.  SVAE_EBADARG (checked on the host before any device call): a null
+ * pointer, n, ny or c <= 0, n not a multiple of ny, h or w < SVAE_SSIM_WINDOW, data_range <= 0 or NaN. */
+#define SVAE_SSIM_WINDOW 11
+#define SVAE_SSIM_SIGMA 1.5
+#define SVAE_SSIM_K1 0.01
+#define SVAE_SSIM_K2 0.03
+#define SVAE_METRICS_TILE 16
+int svae_op_image_metrics(const float* x, int n, const float* y, int ny, int h, int w, int c, float data_range,
+                          double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3804,4 +3804,18 @@ int svae_op_tensor_stats(const float* x, const int64_t* plan, int32_t n_seg, int
   return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
 }
 
+int svae_op_image_metrics(const float* x, int n, const float* y, int ny, int h, int w, int c, float data_range,
+                          double* out, void* stream) {
+  if (!x || !y || !out) return fail(nullptr, SVAE_EBADARG, "image_metrics: null pointer");
+  if (n <= 0 || ny <= 0 || c <= 0) return fail(nullptr, SVAE_EBADARG, "image_metrics: n, ny and c must be positive");
+  if (n % ny != 0) return fail(nullptr, SVAE_EBADARG, "image_metrics: n must be a multiple of ny");
+  if (h < SVAE_SSIM_WINDOW || w < SVAE_SSIM_WINDOW)
+    return fail(nullptr, SVAE_EBADARG, "image_metrics: h and w must hold one " + std::to_string(SVAE_SSIM_WINDOW) +
+                                           "-wide window");
+  if (!(data_range > 0.f)) return fail(nullptr, SVAE_EBADARG, "image_metrics: data_range must be > 0");
+  image_metrics(x, n, y, ny, h, w, c, data_range, out, (hipStream_t)stream);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
+}
+
 }  // extern "C"

@@ -360,6 +360,10 @@ long long stats_plan(const long long* offsets, const long long* lengths, int n_s
 // part: n_chunks * 8 doubles; out: n_seg * 8 doubles; at most two launches on s
 void tensor_stats(const float* x, const long long* plan, int n_seg, long long n_chunks, float c, double* part,
                   double* out, hipStream_t s);
+// ---- image metrics (metrics.hip): the four fp64 columns of svae_op_image_metrics per image, one launch on s ----
+// image i of x [n,h,w,c] against image i % ny of y; arguments as checked by the entry point (h, w >= 11)
+void image_metrics(const float* x, int n, const float* y, int ny, int h, int w, int c, float data_range, double* out,
+                   hipStream_t s);
 // column sums of X [rows][C<=4] -> out0[0..n0), out1[0..C-n0)   (part: scratch >= 1024 floats)
 void colsum_small(const float* X, int ld, long long rows, int C, float* part, float* out0, int n0, float* out1,
                   hipStream_t s);

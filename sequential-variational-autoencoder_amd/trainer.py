@@ -31,9 +31,10 @@ class NoisyTrainer:
     log_loss_freq = 20
     save_freq = 2000           # sequential_vae.py:254
     test_seed_xor = 0x7E577E57A5A5A5A5  # test-noise key = seed ^ this
+    eval_seed_xor = 0xE7A1E7A15C0DE5ED  # evaluate()'s corruption key = its seed ^ this
 
     def __init__(self, network, dataset, denoise_train=False, vis_frequency=1000, plot_reconstruction=False,
-                 base_dir=None, logger=None, seed=0, summary_freq=0):
+                 base_dir=None, logger=None, seed=0, summary_freq=0, eval_frequency=0):
         if list(dataset.data_dims) != list(network.data_dims):
             raise ValueError("dataset images %s, network %s" % (dataset.data_dims, network.data_dims))
         if tuple(dataset.range) != tuple(float(v) for v in network.cfg.range):
@@ -50,6 +51,10 @@ class NoisyTrainer:
         # every summary_freq-th step appends network.summaries() to <base_dir>/summaries.jsonl (the reference's
         # tb_summary_freq is 10); 0: none, and the step is exactly what it is without this option
         self.summary_freq = int(summary_freq)
+        # every eval_frequency-th step appends evaluate() to <base_dir>/evaluation.jsonl; 0: none, and the loop is
+        # exactly what it is without this option
+        self.eval_frequency = int(eval_frequency)
+        self._eval_stack = self._eval_rows = None  # evaluate()'s kept device buffers
         self.batch_size = network.batch_size
         self.data_dims = list(dataset.data_dims)
         self.device = network.device
@@ -115,6 +120,8 @@ class NoisyTrainer:
         self.iteration += 1
         if self.summary_freq > 0 and self.iteration % self.summary_freq == 0:
             self.write_summaries()
+        if self.eval_frequency > 0 and self.iteration % self.eval_frequency == 0:
+            self.write_evaluation()  # after the summaries: they describe the training forward
         return loss
 
     def write_summaries(self):
@@ -170,6 +177,116 @@ class NoisyTrainer:
             if i == 0 and self.plot_reconstruction_enabled:
                 self.plot_reconstruction(epoch, tgt, inp, net.xhat(-1))
         return float(err) / n
+
+    # ------------------------------------------------------------------ held-out evaluation
+    def evaluate(self, split="test", num_batches=None, seed=None):
+        """Quality of every chain step on a fixed validation set: the whole ``split`` ("test" or "train"), each
+        image once, scored against the clean image in PSNR and SSIM (metrics.image_metrics), with the corrupted
+        input as the baseline.
+
+        The split is walked in windows of B from 0; a last partial window is [N - B, N), of which only the rows
+        not yet counted enter the means (N < B raises).  ``num_batches`` = k limits the walk to the first k whole
+        windows.  Nothing of the training run moves: not the dataset cursors, not train_offset / test_offset,
+        not the parameters, the Adam state or the iteration, and not the network's device Philox counter,
+        because every draw is injected.  With denoise_train the corruption is svae_op_make_batch under the key
+        ``seed ^ eval_seed_xor`` from offset 0 (advancing by one batch per window); eps [T,B,Dz] and then, under
+        add_noise_to_chain, the chain noise [T,B,H,W,C] of every window come from one
+        ``torch.Generator(device).manual_seed(seed)`` made at the start.  ``seed`` defaults to the trainer's.
+        Every evaluation of a split therefore scores the same corrupted images with the same draws.
+
+        Per window: forward(input, target, eps, 1.0, noise), x_hat_t copied into slots 1 .. T of a kept
+        [T + 1, B, H, W, C] stack whose slot 0 is the input, one metrics launch, and sums into a device fp64
+        table; one device -> host copy at the end.  Returns
+
+            {"split", "images", "seed", "input": {"mse", "psnr", "ssim"},
+             "steps": [{"mse", "psnr", "ssim", "recon", "kl"} for every t], "error_per_pixel", "elbo"}
+
+        where every number is a mean over the images: psnr the mean of the per-image values (with L = hi - lo;
+        +inf for an image reproduced exactly, as the input is without denoise_train), recon and kl the per-image
+        SVAE_BUF_REC_IMG / SVAE_BUF_KL_IMG of step t, error_per_pixel the reference's
+        sum (x_hat_{T-1} - x)^2 / (H W) (trainer.py:131), elbo the per-image loss at reg_coeff 1.0.
+
+        Afterwards the network's last forward is the evaluation's last window: summaries() reads the last
+        forward, so call it before evaluating (step() does)."""
+        net, ds = self.network, self.dataset
+        if getattr(net.cfg, "external_generator_from", 0):
+            raise ValueError("the PixelVAE head is not a trainer network")
+        if split not in ("test", "train"):
+            raise ValueError("split must be 'test' or 'train', got %r" % (split,))
+        from . import metrics
+        data = ds.test if split == "test" else ds.train
+        N, B, T = int(data.shape[0]), self.batch_size, net.cfg.mc_steps
+        H, W, C = self.data_dims
+        if N < B:
+            raise ValueError("batch %d exceeds the %d images of the %s split" % (B, N, split))
+        seed = self.seed if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF
+        windows = [(s, B) for s in range(0, N - B + 1, B)]  # (start, rows not yet counted)
+        if num_batches is not None:
+            windows = windows[:max(0, int(num_batches))]
+        elif N % B:
+            windows.append((N - B, N % B))
+        images = sum(f for _, f in windows)
+        if images == 0:
+            raise ValueError("evaluate needs at least one window")
+        lo, hi = ds.range
+        L, per = hi - lo, H * W * C
+        gen = torch.Generator(device=self.device).manual_seed(seed)
+        if self._eval_stack is None:
+            self._eval_stack = torch.empty([T + 1, B, H, W, C], dtype=torch.float32, device=self.device)
+            self._eval_rows = torch.empty([(T + 1) * B, metrics.COLS], dtype=torch.float64, device=self.device)
+        stack, rows = self._eval_stack, self._eval_rows
+        # columns: sum of mse, psnr, ssim, recon, kl per slot (slot 0: the input, no recon / kl); elbo beside it
+        table = torch.zeros([T + 1, 5], dtype=torch.float64, device=self.device)
+        elbo = torch.zeros((), dtype=torch.float64, device=self.device)
+        stream = _lib.stream_ptr(torch.cuda.current_stream(self.device))
+        offset = 0
+        for start, fresh in windows:
+            if self.denoise_train:
+                self._make_batch(data, start, self._target, self._input, seed ^ self.eval_seed_xor, offset)
+                offset += self._groups()
+                inp = self._input
+            else:
+                self._make_batch(data, start, self._target, None, 0, 0, noise=False)
+                inp = self._target
+            eps = torch.randn([T, B, net.cfg.latent_dim], generator=gen, dtype=torch.float32, device=self.device)
+            noise = None
+            if net.cfg.add_noise_to_chain:
+                noise = torch.randn([T, B, H, W, C], generator=gen, dtype=torch.float32, device=self.device)
+            net.forward(inp, self._target, eps, 1.0, noise=noise)
+            stack[0].copy_(inp)
+            for t in range(T):
+                _lib.check(net.L.svae_copy_out(net.ctx, _lib.BUF_XHAT, t, _lib.ptr(stack[1 + t]), B * per, stream),
+                           net.ctx)
+            m = metrics.image_metrics(stack, self._target, L, out=rows).view(T + 1, B, metrics.COLS)[:, B - fresh:]
+            table[:, 0] += (m[:, :, metrics.COL_SSE] / per).sum(1)
+            table[:, 1] += metrics.psnr(m[:, :, metrics.COL_SSE], per, L).sum(1)
+            table[:, 2] += m[:, :, metrics.COL_SSIM].sum(1)
+            for col, which in ((3, _lib.BUF_REC_IMG), (4, _lib.BUF_KL_IMG)):
+                per_step = torch.stack([net.copy_out(which, t, B) for t in range(T)])
+                table[1:, col] += per_step[:, B - fresh:].double().sum(1)
+            elbo += net.elbo_per_image()[B - fresh:].sum()
+        host = (torch.cat([table.reshape(-1), elbo.reshape(1)]) / images).cpu().tolist()
+        mean = lambda slot, col: host[slot * 5 + col]
+        res = {"split": split, "images": images, "seed": seed,
+               "input": {"mse": mean(0, 0), "psnr": mean(0, 1), "ssim": mean(0, 2)},
+               "steps": [{"mse": mean(1 + t, 0), "psnr": mean(1 + t, 1), "ssim": mean(1 + t, 2),
+                          "recon": mean(1 + t, 3), "kl": mean(1 + t, 4)} for t in range(T)]}
+        res["error_per_pixel"] = res["steps"][-1]["mse"] * C  # sum / (H W) = mse * C
+        res["elbo"] = host[-1]
+        return res
+
+    def write_evaluation(self, **kw):
+        """One line {"iteration", <evaluate(**kw)>}: logged at info level and, with a base_dir, appended to
+        <base_dir>/evaluation.jsonl (a resumed run goes on in the same file)."""
+        row = {"iteration": self.iteration}
+        row.update(self.evaluate(**kw))
+        line = json.dumps(row)
+        self.LOG.info(line)
+        if self.base_dir is not None:
+            os.makedirs(self.base_dir, exist_ok=True)
+            with open(os.path.join(self.base_dir, "evaluation.jsonl"), "a") as f:
+                f.write(line + "\n")
+        return row
 
     def plot_reconstruction(self, train_epoch, original_images, noisy_images, reconstructed_images, num_plot=3):
         """original | noisy | reconstruction of the first num_plot images (canvas.reconstruction_canvas);

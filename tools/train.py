@@ -34,6 +34,9 @@ def parse(argv=None):
     ap.add_argument("--summary_freq", type=int, default=0,
                     help="append the training summaries to <model dir>/summaries.jsonl every N iterations "
                          "(0: off; the reference's tb_summary_freq is 10)")
+    ap.add_argument("--eval_frequency", type=int, default=0,
+                    help="append NoisyTrainer.evaluate() of the test split (per-step PSNR / SSIM on a fixed "
+                         "validation set) to <model dir>/evaluation.jsonl every N iterations (0: off)")
     ap.add_argument("--iters", type=int, default=None, help="iterations to run (default: the reference's 10^7)")
     ap.add_argument("--dtype", default="bf16x6", choices=["fp32", "bf16", "bf16x6"])
     ap.add_argument("--models_dir", default="models")
@@ -81,7 +84,7 @@ def main(argv=None):
     net.name = a.netname
     trainer = NT(net, ds, denoise_train=a.denoise_train, vis_frequency=a.vis_frequency,
                  plot_reconstruction=a.plot_reconstruction, base_dir=base_dir, logger=log, seed=a.seed,
-                 summary_freq=a.summary_freq)
+                 summary_freq=a.summary_freq, eval_frequency=a.eval_frequency)
     if a.continue_training and os.path.exists(os.path.join(base_dir, "trainer.json")):
         trainer.load(base_dir)
         log.info("resumed at iteration %d" % trainer.iteration)
