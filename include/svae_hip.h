@@ -439,6 +439,32 @@ int svae_op_tensor_stats(const float* x, const int64_t* plan, int32_t n_seg, int
 int svae_op_image_metrics(const float* x, int n, const float* y, int ny, int h, int w, int c, float data_range,
                           double* out, void* stream);
 
+/* Log-density of query points under an equal-weight mixture of diagonal Gaussians, per group of dimensions, without
+ * the 1 / nm (no reference counterpart: the numbers behind NoisyTrainer.latent_information).  z [nq] rows ldz
+ * floats apart, mu and sigma [nm] rows ldm floats apart (fp32, device, any base alignment, ldz, ldm >= d); seg is a
+ * HOST array of n_seg (offset, length) pairs, dimension sets S = [offset, offset + length) of [0, d) that may
+ * overlap and come in any order.  Row n of out [nq][n_seg] (fp64, device; nothing else is written):
+ *   out[n][s] = log sum_{m < nm} exp( sum_{j in S} ( -((z[n][j] - mu[m][j]) / sigma[m][j])^2 / 2
+ *                                                    - log sigma[m][j] - log(2 pi) / 2 ) )
+ * All arithmetic after the load is fp64 in an order fixed by the shapes (csrc/latents.hip): the dimensions of S in
+ * ascending order, then a streaming logsumexp over the components in ascending m.  out[n][s] depends on z[n], the
+ * components and the segment only: not on nq, on the other segments, on the launch or on an address; two calls give
+ * the same bytes.  No [nq, nm] intermediate exists: components are staged in tiles of SVAE_LATENTS_TILE.  The
+ * segments travel as kernel arguments, sixteen consecutive ones to a block: one launch on `stream` per run of up
+ * to 256 segments whose groups of sixteen span alike many dimensions (<= 16, 64, 128 or 256), so one or two
+ * launches for a whole / levels / single-dimensions list; no allocation, no synchronisation.  sigma > 0 and finite is the
+ * caller's contract: a
+ * component or query that breaks it (or a NaN) makes the rows that read it non-finite and nothing else.
+ * SVAE_EBADARG (checked on the host before any launch): a null pointer, nq, nm, d or n_seg <= 0, ldz or ldm < d, a
+ * segment with length < 1 or outside [0, d).  SVAE_EBADCONFIG: d > SVAE_LATENTS_MAX_DIM, n_seg >
+ * SVAE_LATENTS_MAX_SEGMENTS, nq > 2^31 - 1. */
+#define SVAE_LATENTS_TILE 16
+#define SVAE_LATENTS_MAX_DIM 256
+#define SVAE_LATENTS_MAX_SEGMENTS 1024
+int svae_op_mixture_logdensity(const float* z, int64_t nq, int64_t ldz, const float* mu, const float* sigma,
+                               int64_t nm, int64_t ldm, int d, const int32_t* seg, int n_seg, double* out,
+                               void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3818,4 +3818,25 @@ int svae_op_image_metrics(const float* x, int n, const float* y, int ny, int h, 
   return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
 }
 
+int svae_op_mixture_logdensity(const float* z, int64_t nq, int64_t ldz, const float* mu, const float* sigma,
+                               int64_t nm, int64_t ldm, int d, const int32_t* seg, int n_seg, double* out,
+                               void* stream) {
+  if (!z || !mu || !sigma || !seg || !out) return fail(nullptr, SVAE_EBADARG, "mixture_logdensity: null pointer");
+  if (nq <= 0 || nm <= 0 || d <= 0 || n_seg <= 0)
+    return fail(nullptr, SVAE_EBADARG, "mixture_logdensity: nq, nm, d and n_seg must be positive");
+  if (d > SVAE_LATENTS_MAX_DIM || n_seg > SVAE_LATENTS_MAX_SEGMENTS || nq > 2147483647LL)
+    return fail(nullptr, SVAE_EBADCONFIG, "mixture_logdensity: at most " + std::to_string(SVAE_LATENTS_MAX_DIM) +
+                                              " dimensions, " + std::to_string(SVAE_LATENTS_MAX_SEGMENTS) +
+                                              " segments and 2^31 - 1 query rows");
+  if (ldz < d || ldm < d) return fail(nullptr, SVAE_EBADARG, "mixture_logdensity: a leading dimension below d");
+  for (int i = 0; i < n_seg; ++i) {
+    const int64_t off = seg[2 * i], len = seg[2 * i + 1];
+    if (off < 0 || len < 1 || off + len > d)
+      return fail(nullptr, SVAE_EBADARG, "mixture_logdensity: segment " + std::to_string(i) + " is not inside [0, d)");
+  }
+  mixture_logdensity(z, nq, ldz, mu, sigma, nm, ldm, seg, n_seg, out, (hipStream_t)stream);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
+}
+
 }  // extern "C"

@@ -364,6 +364,10 @@ void tensor_stats(const float* x, const long long* plan, int n_seg, long long n_
 // image i of x [n,h,w,c] against image i % ny of y; arguments as checked by the entry point (h, w >= 11)
 void image_metrics(const float* x, int n, const float* y, int ny, int h, int w, int c, float data_range, double* out,
                    hipStream_t s);
+// ---- mixture log-density (latents.hip): svae_op_mixture_logdensity's [nq][n_seg] fp64 table, launches on s ----
+// seg: host (offset, length) pairs; arguments as checked by the entry point
+void mixture_logdensity(const float* z, long long nq, long long ldz, const float* mu, const float* sigma,
+                        long long nm, long long ldm, const int* seg, int n_seg, double* out, hipStream_t s);
 // column sums of X [rows][C<=4] -> out0[0..n0), out1[0..C-n0)   (part: scratch >= 1024 floats)
 void colsum_small(const float* X, int ld, long long rows, int C, float* part, float* out0, int n0, float* out1,
                   hipStream_t s);

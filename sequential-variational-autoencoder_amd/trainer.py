@@ -12,6 +12,7 @@ state_dict(), so a resumed run corrupts its next batch exactly as the uninterrup
 """
 import json
 import logging
+import math
 import os
 import time
 
@@ -34,7 +35,7 @@ class NoisyTrainer:
     eval_seed_xor = 0xE7A1E7A15C0DE5ED  # evaluate()'s corruption key = its seed ^ this
 
     def __init__(self, network, dataset, denoise_train=False, vis_frequency=1000, plot_reconstruction=False,
-                 base_dir=None, logger=None, seed=0, summary_freq=0, eval_frequency=0):
+                 base_dir=None, logger=None, seed=0, summary_freq=0, eval_frequency=0, info_frequency=0):
         if list(dataset.data_dims) != list(network.data_dims):
             raise ValueError("dataset images %s, network %s" % (dataset.data_dims, network.data_dims))
         if tuple(dataset.range) != tuple(float(v) for v in network.cfg.range):
@@ -54,6 +55,9 @@ class NoisyTrainer:
         # every eval_frequency-th step appends evaluate() to <base_dir>/evaluation.jsonl; 0: none, and the loop is
         # exactly what it is without this option
         self.eval_frequency = int(eval_frequency)
+        # every info_frequency-th step appends latent_information() to <base_dir>/latent_information.jsonl; 0: none,
+        # and the loop is exactly what it is without this option
+        self.info_frequency = int(info_frequency)
         self._eval_stack = self._eval_rows = None  # evaluate()'s kept device buffers
         self.batch_size = network.batch_size
         self.data_dims = list(dataset.data_dims)
@@ -122,6 +126,8 @@ class NoisyTrainer:
             self.write_summaries()
         if self.eval_frequency > 0 and self.iteration % self.eval_frequency == 0:
             self.write_evaluation()  # after the summaries: they describe the training forward
+        if self.info_frequency > 0 and self.iteration % self.info_frequency == 0:
+            self.write_latent_information()
         return loss
 
     def write_summaries(self):
@@ -285,6 +291,96 @@ class NoisyTrainer:
         if self.base_dir is not None:
             os.makedirs(self.base_dir, exist_ok=True)
             with open(os.path.join(self.base_dir, "evaluation.jsonl"), "a") as f:
+                f.write(line + "\n")
+        return row
+
+    # ------------------------------------------------------------------ what the latent code carries
+    def latent_information(self, split="test", num_batches=None, seed=None):
+        """Per chain step, how much information the latent code carries about the image and how far the aggregate
+        posterior is from the prior (latents.information: mutual information, marginal KL, total correlation,
+        active units), for the whole code, every ladder level and every single dimension.
+
+        The split is walked exactly as evaluate() walks it: the same windows (a last partial window [N - B, N) of
+        which only the rows not yet counted are kept; ``num_batches`` = k the first k whole windows), the same
+        corruption key ``seed ^ eval_seed_xor`` from offset 0, the same ``torch.Generator(device).manual_seed(seed)``
+        stream with eps drawn first and then the chain noise under add_noise_to_chain, forward at reg_coeff 1.0.
+        The report therefore describes the very forwards that evaluate(seed=...) scores, and like it moves nothing
+        of the training run: no cursor, no offset, no parameter, no Adam state, not the iteration and not the
+        device Philox counter.  It raises as evaluate() does for the PixelVAE head, N < B and a bad split.
+
+        Per window SVAE_BUF_MU, _SIGMA and _Z of every step are copied into kept [T, images, Dz] device tensors;
+        after the walk one latents.information per step (the posterior mean is the clipped one,
+        clamp(SVAE_BUF_MU, +-latent_mean_clip)) and one device -> host copy.  Returns
+
+            {"split", "images", "seed", "mi_ceiling", "prior_stddev" | None,
+             "steps": [{"all": {"mi", "marginal_kl", "kl_sample", "kl", "tc", "active_units"},
+                        "levels": [{the same, with that level's tc} for every level],
+                        "dims": {"mi": [Dz], "marginal_kl": [Dz], "kl": [Dz]}} for every t],
+             "nonfinite"}
+
+        ``mi`` saturates at ``mi_ceiling`` = log(images): see latents.py.  Under use_uniform_prior prior_stddev,
+        marginal_kl, kl_sample and kl are None.  Afterwards the network's last forward is the walk's last window."""
+        net, ds = self.network, self.dataset
+        if getattr(net.cfg, "external_generator_from", 0):
+            raise ValueError("the PixelVAE head is not a trainer network")
+        if split not in ("test", "train"):
+            raise ValueError("split must be 'test' or 'train', got %r" % (split,))
+        from . import latents
+        data = ds.test if split == "test" else ds.train
+        N, B, T, Dz = int(data.shape[0]), self.batch_size, net.cfg.mc_steps, net.cfg.latent_dim
+        H, W, C = self.data_dims
+        if N < B:
+            raise ValueError("batch %d exceeds the %d images of the %s split" % (B, N, split))
+        seed = self.seed if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF
+        windows = [(s, B) for s in range(0, N - B + 1, B)]  # (start, rows not yet counted)
+        if num_batches is not None:
+            windows = windows[:max(0, int(num_batches))]
+        elif N % B:
+            windows.append((N - B, N % B))
+        images = sum(f for _, f in windows)
+        if images == 0:
+            raise ValueError("latent_information needs at least one window")
+        gen = torch.Generator(device=self.device).manual_seed(seed)
+        kept = torch.empty([3, T, images, Dz], dtype=torch.float32, device=self.device)  # mu, sigma, z
+        offset = done = 0
+        for start, fresh in windows:
+            if self.denoise_train:
+                self._make_batch(data, start, self._target, self._input, seed ^ self.eval_seed_xor, offset)
+                offset += self._groups()
+                inp = self._input
+            else:
+                self._make_batch(data, start, self._target, None, 0, 0, noise=False)
+                inp = self._target
+            eps = torch.randn([T, B, Dz], generator=gen, dtype=torch.float32, device=self.device)
+            noise = None
+            if net.cfg.add_noise_to_chain:
+                noise = torch.randn([T, B, H, W, C], generator=gen, dtype=torch.float32, device=self.device)
+            net.forward(inp, self._target, eps, 1.0, noise=noise)
+            for k, which in enumerate((_lib.BUF_MU, _lib.BUF_SIGMA, _lib.BUF_Z)):
+                for t in range(T):
+                    kept[k, t, done:done + fresh] = net.latent(which, t)[B - fresh:]
+            done += fresh
+        clip = float(net.cfg.latent_mean_clip)
+        mean = kept[0].clamp(-clip, clip) if math.isfinite(clip) else kept[0]
+        prior = None if net.cfg.use_uniform_prior else float(net.cfg.latent_prior_stddev)
+        lay = latents.Layout(latents.segments_for(net.cfg))
+        host = torch.stack([latents.information(kept[2, t], mean[t], kept[1, t], lay.segments, prior)
+                            for t in range(T)]).cpu().tolist()
+        steps = [lay.report(row, prior is None) for row in host]
+        return {"split": split, "images": images, "seed": seed, "mi_ceiling": math.log(images), "prior_stddev": prior,
+                "steps": [{k: s[k] for k in ("all", "levels", "dims")} for s in steps],
+                "nonfinite": sum(s["nonfinite"] for s in steps)}
+
+    def write_latent_information(self, **kw):
+        """One line {"iteration", <latent_information(**kw)>}: logged at info level and, with a base_dir, appended
+        to <base_dir>/latent_information.jsonl (a resumed run goes on in the same file)."""
+        row = {"iteration": self.iteration}
+        row.update(self.latent_information(**kw))
+        line = json.dumps(row)
+        self.LOG.info(line)
+        if self.base_dir is not None:
+            os.makedirs(self.base_dir, exist_ok=True)
+            with open(os.path.join(self.base_dir, "latent_information.jsonl"), "a") as f:
                 f.write(line + "\n")
         return row
 

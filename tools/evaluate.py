@@ -8,6 +8,8 @@ Give the data, --batch_size, --dtype and --denoise_train the run was trained wit
 validation set the run's own --eval_frequency lines scored, and reproduces the last of them when the checkpoint is
 that iteration's.  The seeds come from the run's trainer.json (--synthetic images and, unless --seed is given, the
 evaluation's draws).  Prints the result as one JSON line and writes it to eval.json next to the checkpoint.
+--latent_information reports what the latent code of those same forwards carries instead
+(NoisyTrainer.latent_information, into latent_information.json).
 """
 import argparse
 import importlib
@@ -32,6 +34,9 @@ def parse(argv=None):
     ap.add_argument("--split", default="test", choices=["test", "train"])
     ap.add_argument("--num_batches", type=int, default=None, help="only the first k whole windows")
     ap.add_argument("--seed", type=int, default=None, help="seed of the evaluation's draws (default: the run's)")
+    ap.add_argument("--latent_information", action="store_true",
+                    help="report NoisyTrainer.latent_information() of the same forwards instead (mutual information, "
+                         "marginal KL, total correlation per step); written to latent_information.json")
     ap.add_argument("--dtype", default="bf16x6", choices=["fp32", "bf16", "bf16x6"])
     ap.add_argument("--models_dir", default="models")
     return ap.parse_args(argv)
@@ -72,9 +77,10 @@ def main(argv=None):
     net.load_checkpoint(ckpt)
     trainer = NT(net, ds, denoise_train=a.denoise_train, seed=run_seed)
     row = {"iteration": int(state.get("iteration", net.iteration))}
-    row.update(trainer.evaluate(split=a.split, num_batches=a.num_batches, seed=a.seed))
+    report = trainer.latent_information if a.latent_information else trainer.evaluate
+    row.update(report(split=a.split, num_batches=a.num_batches, seed=a.seed))
     line = json.dumps(row)
-    with open(os.path.join(base_dir, "eval.json"), "w") as f:
+    with open(os.path.join(base_dir, "latent_information.json" if a.latent_information else "eval.json"), "w") as f:
         f.write(line + "\n")
     print(line)
     return 0
