@@ -465,6 +465,42 @@ int svae_op_mixture_logdensity(const float* z, int64_t nq, int64_t ldz, const fl
                                int64_t nm, int64_t ldm, int d, const int32_t* seg, int n_seg, double* out,
                                void* stream);
 
+/* Row-wise statistics of pairwise squared distances (no reference counterpart: the numbers behind
+ * NoisyTrainer.sample_quality).  x is [n] rows of d fp32, ldx floats apart; y, m, ldy are HOST arrays of n_groups
+ * device pointers, row counts and leading dimensions, the column groups (separate tensors: nothing is
+ * concatenated).  Any base alignment, ldx, ldy[g] >= d.  self_group = g >= 0 says the rows ARE group g's points
+ * (x == y[g], n == m[g], row i is column i): the pair (i, i) of that group enters neither output; -1: no exclusion.
+ * inv_two_sigma2 is a HOST array of n_bw values 1 / (2 sigma_l^2).  With d2(i, j) = sum_k (x[i][k] - y_g[j][k])^2,
+ * the outputs (device; nothing else is written) are
+ *   ksum  [n][n_groups][n_bw] (fp64)  = sum_j exp(-d2(i, j) * inv_two_sigma2[l]) over the group's admitted columns,
+ *   nn_d2 [n][n_groups]       (fp64)  = min_j d2(i, j) over the same columns, +inf where there is none,
+ *   nn_idx[n][n_groups]       (int64) = the smallest j that attains the computed minimum, -1 where there is none.
+ * ksum, or nn_d2 and nn_idx together, may be NULL to skip that part; n_bw == 0 requires ksum == NULL.
+ * Numerics (csrc/pairwise.hip): d2 = max(0, (a_i + b_j) - 2 g_ij) in fp64, a and b the squared norms summed in fp64
+ * in an order fixed by d, g_ij the inner product on v_mfma_f32_32x32x2_f32 (exact fp32 products, fp32 accumulation
+ * in ascending k); exp and every sum over j in fp64, ascending j within column tiles of SVAE_PAIRWISE_TILE_COLS,
+ * the tiles in ascending order; no atomics.  Row i of every output depends on x[i], the groups and the bandwidths
+ * only: not on n, on the other rows, on the launch or on an address; two calls give the same bytes.  A NaN or inf
+ * element makes the rows and columns that read it non-finite and nothing else.  The launches go on `stream`; no
+ * allocation, no synchronisation: the caller provides svae_op_pairwise_scratch_bytes(n, m, n_groups, n_bw) bytes
+ * of 8-byte aligned device scratch (norms and per-column-tile partials).
+ * SVAE_EBADARG (checked on the host before any launch): a null required pointer or only one of nn_d2 / nn_idx, n,
+ * d, n_groups or an m[g] <= 0, a leading dimension < d, n_bw < 0, n_bw == 0 with ksum or n_bw > 0 without, nothing
+ * to compute, a bandwidth value <= 0 or non-finite, self_group >= n_groups or set with n != m[self_group] or
+ * x != y[self_group], null scratch.  SVAE_EBADCONFIG: n_groups > SVAE_PAIRWISE_MAX_GROUPS, n_bw >
+ * SVAE_PAIRWISE_MAX_BW, d > 2^31 - 1, more than 65535 row tiles or 2^31 - 1 column tiles.
+ * svae_op_pairwise_scratch_bytes returns -1 for arguments the op would reject. */
+#define SVAE_PAIRWISE_TILE_ROWS 128
+#define SVAE_PAIRWISE_TILE_COLS 128
+#define SVAE_PAIRWISE_TILE_K 32
+#define SVAE_PAIRWISE_MAX_GROUPS 4
+#define SVAE_PAIRWISE_MAX_BW 8
+int64_t svae_op_pairwise_scratch_bytes(int64_t n, const int64_t* m, int n_groups, int n_bw);
+int svae_op_pairwise_stats(const float* x, int64_t n, int64_t ldx, const float* const* y, const int64_t* m,
+                           const int64_t* ldy, int n_groups, int64_t d, int self_group,
+                           const double* inv_two_sigma2, int n_bw, double* ksum, double* nn_d2, int64_t* nn_idx,
+                           void* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

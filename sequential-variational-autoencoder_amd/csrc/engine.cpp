@@ -3839,4 +3839,64 @@ int svae_op_mixture_logdensity(const float* z, int64_t nq, int64_t ldz, const fl
   return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
 }
 
+static bool pairwise_shape_ok(int64_t n, const int64_t* m, int n_groups, int n_bw) {
+  if (!m || n <= 0 || n_groups <= 0 || n_groups > SVAE_PAIRWISE_MAX_GROUPS || n_bw < 0 || n_bw > SVAE_PAIRWISE_MAX_BW)
+    return false;
+  int64_t tiles = 0;
+  for (int g = 0; g < n_groups; ++g) {
+    if (m[g] <= 0) return false;
+    tiles += (m[g] + SVAE_PAIRWISE_TILE_COLS - 1) / SVAE_PAIRWISE_TILE_COLS;
+  }
+  return tiles <= 2147483647LL && (n + SVAE_PAIRWISE_TILE_ROWS - 1) / SVAE_PAIRWISE_TILE_ROWS <= 65535;
+}
+
+int64_t svae_op_pairwise_scratch_bytes(int64_t n, const int64_t* m, int n_groups, int n_bw) {
+  if (!pairwise_shape_ok(n, m, n_groups, n_bw)) return -1;
+  long long mm[SVAE_PAIRWISE_MAX_GROUPS];
+  for (int g = 0; g < n_groups; ++g) mm[g] = m[g];
+  return pairwise_scratch_bytes(n, mm, n_groups, n_bw);
+}
+
+int svae_op_pairwise_stats(const float* x, int64_t n, int64_t ldx, const float* const* y, const int64_t* m,
+                           const int64_t* ldy, int n_groups, int64_t d, int self_group,
+                           const double* inv_two_sigma2, int n_bw, double* ksum, double* nn_d2, int64_t* nn_idx,
+                           void* scratch, void* stream) {
+  if (!x || !y || !m || !ldy) return fail(nullptr, SVAE_EBADARG, "pairwise_stats: null pointer");
+  if (n <= 0 || d <= 0 || n_groups <= 0 || n_bw < 0)
+    return fail(nullptr, SVAE_EBADARG, "pairwise_stats: n, d and n_groups must be positive, n_bw not negative");
+  if (n_groups > SVAE_PAIRWISE_MAX_GROUPS || n_bw > SVAE_PAIRWISE_MAX_BW)
+    return fail(nullptr, SVAE_EBADCONFIG, "pairwise_stats: at most " + std::to_string(SVAE_PAIRWISE_MAX_GROUPS) +
+                                              " groups and " + std::to_string(SVAE_PAIRWISE_MAX_BW) + " bandwidths");
+  if ((n_bw == 0) != (ksum == nullptr))
+    return fail(nullptr, SVAE_EBADARG, "pairwise_stats: ksum goes with n_bw > 0 and only with it");
+  if ((nn_d2 == nullptr) != (nn_idx == nullptr))
+    return fail(nullptr, SVAE_EBADARG, "pairwise_stats: nn_d2 and nn_idx come together");
+  if (!ksum && !nn_d2) return fail(nullptr, SVAE_EBADARG, "pairwise_stats: nothing to compute");
+  if (n_bw > 0 && !inv_two_sigma2) return fail(nullptr, SVAE_EBADARG, "pairwise_stats: null bandwidths");
+  if (ldx < d) return fail(nullptr, SVAE_EBADARG, "pairwise_stats: ldx below d");
+  for (int g = 0; g < n_groups; ++g) {
+    if (!y[g]) return fail(nullptr, SVAE_EBADARG, "pairwise_stats: null group " + std::to_string(g));
+    if (m[g] <= 0) return fail(nullptr, SVAE_EBADARG, "pairwise_stats: group " + std::to_string(g) + " is empty");
+    if (ldy[g] < d) return fail(nullptr, SVAE_EBADARG, "pairwise_stats: ldy below d in group " + std::to_string(g));
+  }
+  for (int l = 0; l < n_bw; ++l)
+    if (!(inv_two_sigma2[l] > 0.0) || !std::isfinite(inv_two_sigma2[l]))
+      return fail(nullptr, SVAE_EBADARG, "pairwise_stats: bandwidth " + std::to_string(l) + " is not positive and finite");
+  if (self_group >= n_groups) return fail(nullptr, SVAE_EBADARG, "pairwise_stats: self_group names no group");
+  if (self_group >= 0 && (n != m[self_group] || x != y[self_group]))
+    return fail(nullptr, SVAE_EBADARG, "pairwise_stats: self_group needs x == y[self_group] and n == m[self_group]");
+  if (d > 2147483647LL || !pairwise_shape_ok(n, m, n_groups, n_bw))
+    return fail(nullptr, SVAE_EBADCONFIG, "pairwise_stats: d above 2^31 - 1, or too many row or column tiles");
+  if (!scratch) return fail(nullptr, SVAE_EBADARG, "pairwise_stats: null scratch");
+  long long mm[SVAE_PAIRWISE_MAX_GROUPS], ll[SVAE_PAIRWISE_MAX_GROUPS];
+  for (int g = 0; g < n_groups; ++g) {
+    mm[g] = m[g];
+    ll[g] = ldy[g];
+  }
+  pairwise_stats(x, n, ldx, y, mm, ll, n_groups, (int)d, self_group < 0 ? -1 : self_group, inv_two_sigma2, n_bw, ksum,
+                 nn_d2, (long long*)nn_idx, scratch, (hipStream_t)stream);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
+}
+
 }  // extern "C"

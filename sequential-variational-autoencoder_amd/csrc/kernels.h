@@ -368,6 +368,12 @@ void image_metrics(const float* x, int n, const float* y, int ny, int h, int w, 
 // seg: host (offset, length) pairs; arguments as checked by the entry point
 void mixture_logdensity(const float* z, long long nq, long long ldz, const float* mu, const float* sigma,
                         long long nm, long long ldm, const int* seg, int n_seg, double* out, hipStream_t s);
+// ---- pairwise-distance statistics (pairwise.hip): svae_op_pairwise_stats, launches on s ----
+// y, m, ldy, inv_two_sigma2: host arrays; arguments as checked by the entry point
+long long pairwise_scratch_bytes(long long n, const long long* m, int n_groups, int n_bw);
+void pairwise_stats(const float* x, long long n, long long ldx, const float* const* y, const long long* m,
+                    const long long* ldy, int n_groups, int d, int self_group, const double* inv_two_sigma2,
+                    int n_bw, double* ksum, double* nn_d2, long long* nn_idx, void* scratch, hipStream_t s);
 // column sums of X [rows][C<=4] -> out0[0..n0), out1[0..C-n0)   (part: scratch >= 1024 floats)
 void colsum_small(const float* X, int ld, long long rows, int C, float* part, float* out0, int n0, float* out1,
                   hipStream_t s);

@@ -35,7 +35,8 @@ class NoisyTrainer:
     eval_seed_xor = 0xE7A1E7A15C0DE5ED  # evaluate()'s corruption key = its seed ^ this
 
     def __init__(self, network, dataset, denoise_train=False, vis_frequency=1000, plot_reconstruction=False,
-                 base_dir=None, logger=None, seed=0, summary_freq=0, eval_frequency=0, info_frequency=0):
+                 base_dir=None, logger=None, seed=0, summary_freq=0, eval_frequency=0, info_frequency=0,
+                 quality_frequency=0):
         if list(dataset.data_dims) != list(network.data_dims):
             raise ValueError("dataset images %s, network %s" % (dataset.data_dims, network.data_dims))
         if tuple(dataset.range) != tuple(float(v) for v in network.cfg.range):
@@ -58,6 +59,9 @@ class NoisyTrainer:
         # every info_frequency-th step appends latent_information() to <base_dir>/latent_information.jsonl; 0: none,
         # and the loop is exactly what it is without this option
         self.info_frequency = int(info_frequency)
+        # every quality_frequency-th step appends sample_quality() to <base_dir>/sample_quality.jsonl; 0: none, and
+        # the loop is exactly what it is without this option
+        self.quality_frequency = int(quality_frequency)
         self._eval_stack = self._eval_rows = None  # evaluate()'s kept device buffers
         self.batch_size = network.batch_size
         self.data_dims = list(dataset.data_dims)
@@ -128,6 +132,8 @@ class NoisyTrainer:
             self.write_evaluation()  # after the summaries: they describe the training forward
         if self.info_frequency > 0 and self.iteration % self.info_frequency == 0:
             self.write_latent_information()
+        if self.quality_frequency > 0 and self.iteration % self.quality_frequency == 0:
+            self.write_sample_quality()
         return loss
 
     def write_summaries(self):
@@ -381,6 +387,120 @@ class NoisyTrainer:
         if self.base_dir is not None:
             os.makedirs(self.base_dir, exist_ok=True)
             with open(os.path.join(self.base_dir, "latent_information.jsonl"), "a") as f:
+                f.write(line + "\n")
+        return row
+
+    # ------------------------------------------------------------------ how good the samples are
+    def sample_quality(self, split="test", num_batches=None, seed=None, train_images=None):
+        """Per chain step, how close generated samples x_hat_t are to held-out images and whether they copy
+        training images: the kernel MMD^2 two-sample estimate, the leave-one-out 1-nearest-neighbour two-sample
+        accuracy and nearest-neighbour distances (quality.two_sample), all on svae_op_pairwise_stats.
+
+        The real set R is the ``split`` ("test" or "train") walked in whole windows of B from 0, clean
+        (dequantised, never corrupted); ``num_batches`` = k keeps the first k windows.  A trailing partial window
+        is dropped here (unlike evaluate(): every generated window is a whole batch, and the two sets are kept
+        alike large); N = images < 2 B raises, since the unbiased estimate needs two points per set and one window
+        shares one BatchNorm batch.  The generated sets come from N / B calls of network.generate(z, noise): z
+        [T,B,Dz] and then, under add_noise_to_chain, the chain noise [T,B,H,W,C] of every window are drawn from
+        one ``torch.Generator(device).manual_seed(seed)`` made at the start (``seed`` defaults to the trainer's),
+        z before noise.  z is N(0, 1) also under use_uniform_prior: that is what svae_generate itself draws when
+        no z is given, whatever the prior.  Every draw is injected, so nothing of the training run moves: not the
+        dataset cursors, not train_offset / test_offset, not the parameters, the Adam state or the iteration, and
+        not the network's device Philox counter.  The PixelVAE head and a bad split raise as in evaluate().
+
+        x_hat_t of every window and R are kept as one [T + 1, N, D] device tensor, centred on R's mean row (the
+        distances do not change, the inner products' rounding shrinks).  Per step quality.two_sample(X_t, R)
+        at the bandwidths sigma0^2 * bandwidth_scales of R, the R-against-R pass computed once.  The memorisation
+        check is one nearest-neighbour pass of all (T + 1) N rows against the first ``train_images`` training
+        images (default min(train size, N); clean, dequantised window by window): nn_train of a step far below
+        nn_train of "real" says the samples sit closer to the training set than held-out images do, which is
+        copying.  One device -> host copy at the end.  Returns
+
+            {"split", "images", "seed", "sigma0", "bandwidth_scales", "train_images",
+             "real": {"nn_train": {"mean", "median", "min"}},
+             "steps": [{"mmd2": [5], "mmd2_at_sigma0", "nn_accuracy": {"samples", "real", "all"},
+                        "nn_real": {"mean", "median", "min"}, "nn_train": {...}} for every t],
+             "nonfinite"}
+
+        with every distance a per-element RMS, sqrt(d2 / D), and sigma0 in the units of d (not per element).
+        generate invalidates the network's last training forward: summaries() must be read before (step() does)."""
+        net, ds = self.network, self.dataset
+        if getattr(net.cfg, "external_generator_from", 0):
+            raise ValueError("the PixelVAE head is not a trainer network")
+        if split not in ("test", "train"):
+            raise ValueError("split must be 'test' or 'train', got %r" % (split,))
+        from . import quality
+        data = ds.test if split == "test" else ds.train
+        B, T, Dz = self.batch_size, net.cfg.mc_steps, net.cfg.latent_dim
+        H, W, C = self.data_dims
+        D = H * W * C
+        nwin = int(data.shape[0]) // B
+        if num_batches is not None:
+            nwin = min(nwin, max(0, int(num_batches)))
+        N = nwin * B
+        if N < 2 * B:
+            raise ValueError("sample_quality needs at least two whole windows of %d images, the %s split gives %d"
+                             % (B, split, nwin))
+        M = int(ds.train.shape[0])
+        M = min(M, N) if train_images is None else int(train_images)
+        if M < 1 or M > int(ds.train.shape[0]) or int(ds.train.shape[0]) < B:
+            raise ValueError("train_images must be in [1, %d] and the training set hold a batch" % int(ds.train.shape[0]))
+        seed = self.seed if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF
+        gen = torch.Generator(device=self.device).manual_seed(seed)
+        kept = torch.empty([T + 1, N, D], dtype=torch.float32, device=self.device)  # X_0 .. X_{T-1}, R
+        for w in range(nwin):
+            self._make_batch(data, w * B, self._target, None, 0, 0, noise=False)
+            kept[T, w * B:(w + 1) * B] = self._target.view(B, D)
+            z = torch.randn([T, B, Dz], generator=gen, dtype=torch.float32, device=self.device)
+            noise = None
+            if net.cfg.add_noise_to_chain:
+                noise = torch.randn([T, B, H, W, C], generator=gen, dtype=torch.float32, device=self.device)
+            for t, xh in enumerate(net.generate(z, noise=noise)):
+                kept[t, w * B:(w + 1) * B] = xh.reshape(B, D)
+        train = torch.empty([M, D], dtype=torch.float32, device=self.device)
+        for start in range(0, M, B):
+            s = min(start, int(ds.train.shape[0]) - B)
+            self._make_batch(ds.train, s, self._target, None, 0, 0, noise=False)
+            rows = min(B, M - start)
+            train[start:start + rows] = self._target.view(B, D)[start - s:start - s + rows]
+        mu = kept[T].double().mean(0).float()
+        kept -= mu
+        train -= mu
+        R = kept[T]
+        bw = quality.bandwidths(R)
+        bwl = bw.tolist()  # (the one early device -> host copy: the op takes the bandwidths on the host)
+        yy = quality.self_sums(R, bwl)
+        tables = [quality.two_sample_device(kept[t], R, bwl, yy=yy) for t in range(T)]
+        _, nd, _ = quality.pairwise_stats(kept.view((T + 1) * N, D), [train], [], ksum=False)
+        rms = (nd.view(T + 1, N) / D).sqrt()
+        nnt = torch.stack([rms.mean(1), quality.median(rms), rms.min(1).values, torch.isnan(rms).sum(1).double()], 1)
+        host = torch.cat([torch.stack(tables).reshape(-1), nnt.reshape(-1)]).cpu().tolist()
+        nb = len(bwl)
+        width = nb + 7
+        nn_train = lambda i: dict(zip(("mean", "median", "min"), host[T * width + 4 * i:T * width + 4 * i + 3]))
+        steps, bad = [], 0
+        for t in range(T):
+            r = quality.unpack(host[t * width:(t + 1) * width], nb)
+            bad += r["nonfinite"] + int(host[T * width + 4 * t + 3])
+            a = r["nn_accuracy"]
+            steps.append({"mmd2": r["mmd2"], "mmd2_at_sigma0": r["mmd2_at_sigma0"],
+                          "nn_accuracy": {"samples": a["x"], "real": a["y"], "all": a["all"]},
+                          "nn_real": r["nn_other"], "nn_train": nn_train(t)})
+        bad += int(host[T * width + 4 * T + 3])
+        return {"split": split, "images": N, "seed": seed, "sigma0": bwl[nb // 2] ** 0.5,
+                "bandwidth_scales": list(quality.SCALES), "train_images": M, "real": {"nn_train": nn_train(T)},
+                "steps": steps, "nonfinite": bad}
+
+    def write_sample_quality(self, **kw):
+        """One line {"iteration", <sample_quality(**kw)>}: logged at info level and, with a base_dir, appended to
+        <base_dir>/sample_quality.jsonl (a resumed run goes on in the same file)."""
+        row = {"iteration": self.iteration}
+        row.update(self.sample_quality(**kw))
+        line = json.dumps(row)
+        self.LOG.info(line)
+        if self.base_dir is not None:
+            os.makedirs(self.base_dir, exist_ok=True)
+            with open(os.path.join(self.base_dir, "sample_quality.jsonl"), "a") as f:
                 f.write(line + "\n")
         return row
 

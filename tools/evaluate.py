@@ -9,7 +9,8 @@ validation set the run's own --eval_frequency lines scored, and reproduces the l
 that iteration's.  The seeds come from the run's trainer.json (--synthetic images and, unless --seed is given, the
 evaluation's draws).  Prints the result as one JSON line and writes it to eval.json next to the checkpoint.
 --latent_information reports what the latent code of those same forwards carries instead
-(NoisyTrainer.latent_information, into latent_information.json).
+(NoisyTrainer.latent_information, into latent_information.json).  --sample_quality scores samples generated from
+prior latents against the split instead (NoisyTrainer.sample_quality, into sample_quality.json).
 """
 import argparse
 import importlib
@@ -37,6 +38,10 @@ def parse(argv=None):
     ap.add_argument("--latent_information", action="store_true",
                     help="report NoisyTrainer.latent_information() of the same forwards instead (mutual information, "
                          "marginal KL, total correlation per step); written to latent_information.json")
+    ap.add_argument("--sample_quality", action="store_true",
+                    help="report NoisyTrainer.sample_quality() instead: per-step kernel MMD^2, 1-nearest-neighbour "
+                         "two-sample accuracy and nearest-training-image distances of generated samples against the "
+                         "split's whole windows; written to sample_quality.json")
     ap.add_argument("--dtype", default="bf16x6", choices=["fp32", "bf16", "bf16x6"])
     ap.add_argument("--models_dir", default="models")
     return ap.parse_args(argv)
@@ -77,10 +82,17 @@ def main(argv=None):
     net.load_checkpoint(ckpt)
     trainer = NT(net, ds, denoise_train=a.denoise_train, seed=run_seed)
     row = {"iteration": int(state.get("iteration", net.iteration))}
-    report = trainer.latent_information if a.latent_information else trainer.evaluate
+    if a.latent_information and a.sample_quality:
+        print("--latent_information and --sample_quality are two reports: ask for one")
+        return 1
+    report, name = trainer.evaluate, "eval.json"
+    if a.latent_information:
+        report, name = trainer.latent_information, "latent_information.json"
+    if a.sample_quality:
+        report, name = trainer.sample_quality, "sample_quality.json"
     row.update(report(split=a.split, num_batches=a.num_batches, seed=a.seed))
     line = json.dumps(row)
-    with open(os.path.join(base_dir, "latent_information.json" if a.latent_information else "eval.json"), "w") as f:
+    with open(os.path.join(base_dir, name), "w") as f:
         f.write(line + "\n")
     print(line)
     return 0

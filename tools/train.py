@@ -41,6 +41,10 @@ def parse(argv=None):
                     help="append NoisyTrainer.latent_information() of the test split (per-step mutual information, "
                          "marginal KL and total correlation of the latent code) to <model dir>/"
                          "latent_information.jsonl every N iterations (0: off)")
+    ap.add_argument("--quality_frequency", type=int, default=0,
+                    help="append NoisyTrainer.sample_quality() against the test split (per-step kernel MMD^2, "
+                         "1-nearest-neighbour two-sample accuracy and nearest-training-image distances of generated "
+                         "samples) to <model dir>/sample_quality.jsonl every N iterations (0: off)")
     ap.add_argument("--iters", type=int, default=None, help="iterations to run (default: the reference's 10^7)")
     ap.add_argument("--dtype", default="bf16x6", choices=["fp32", "bf16", "bf16x6"])
     ap.add_argument("--models_dir", default="models")
@@ -89,7 +93,7 @@ def main(argv=None):
     trainer = NT(net, ds, denoise_train=a.denoise_train, vis_frequency=a.vis_frequency,
                  plot_reconstruction=a.plot_reconstruction, base_dir=base_dir, logger=log, seed=a.seed,
                  summary_freq=a.summary_freq, eval_frequency=a.eval_frequency,
-                 info_frequency=a.info_frequency)
+                 info_frequency=a.info_frequency, quality_frequency=a.quality_frequency)
     if a.continue_training and os.path.exists(os.path.join(base_dir, "trainer.json")):
         trainer.load(base_dir)
         log.info("resumed at iteration %d" % trainer.iteration)
