@@ -376,6 +376,46 @@ int svae_op_make_batch(const void* data, int data_u8, const int32_t* idx, int64_
                        float lo, float hi, float pepper_prob, float salt_prob, float gaussian_scale, uint64_t seed,
                        uint64_t offset, float* target, float* input, void* stream);
 
+/* Structured corruptions of a clean batch in one launch on `stream` (no allocation, no synchronisation; no
+ * reference counterpart: the inputs of inpainting, deblurring and super-resolution runs).  target [n,h,w,c] is the
+ * clean fp32 batch (what svae_op_make_batch writes with input == NULL); input receives the degraded batch and mask
+ * [n,h,w] (may be NULL) 1 where a pixel was cut out, 0 elsewhere.  Per image b, in this order:
+ *   1 blur      with probability p_blur: separable Gaussian, sigma = sigma_lo + u * (sigma_hi - sigma_lo) (the
+ *               difference, the product and the sum each rounded to fp32), r = min(ceil(3 sigma), 12) taps to each
+ *               side (fp32 product, fp32 ceil; r = 0: identity), weights g_k = expf(-k^2 / (2 sigma^2)) divided by
+ *               g_0 + 2 sum_{k=1..r} g_k (the sum in ascending k).  Horizontal pass, then vertical pass, each
+ *               sum_{k=-r..r} w_|k| x[clamp(i + k)] per channel, started from 0 and accumulated in fp32 in
+ *               ascending k, every product and sum rounded on its own; out-of-image taps read the clamped index.
+ *   2 down      with probability p_down (factor > 1): pixel (i, j) becomes the mean of the in-image pixels of its
+ *               block (i / factor, j / factor), per channel: sequential fp32 adds from 0 in row-major order, then one
+ *               correctly rounded fp32 division by the count (edge blocks are partial).
+ *   3 cut-out   with probability p_cut: every pixel inside any of the `boxes` boxes becomes `fill` in all channels.
+ *   4 noise     svae_op_make_batch's contract on the result, word for word: flat element e of the [n*h*w*c] batch,
+ *               group e / 4, counter offset + e / 4, c3 = 0, streams c2 = 0, 1, 2, the same roundings; clip to [lo, hi].
+ * Per-image draws are Philox4x32-10 under the key (lo32(seed), hi32(seed)) with the 64-bit value offset + b in the
+ * counter words (c0, c1), c2 = 3 (a stream make_batch does not use) and c3 = the block index.  Block 0 gives words
+ * a0..a3: blur iff a0 < thr(p_blur), u = (a1 >> 8) * 2^-24, down iff a2 < thr(p_down), cut-out iff a3 < thr(p_cut),
+ * thr as in svae_op_make_batch.  Block 1 + k gives box k from words b0..b3, all integer (mulhi = the high 32 bits of
+ * the 32 x 32 product): bh = min(h, min_side + mulhi(b0, max_side - min_side + 1)), bw likewise from b1 and w,
+ * y0 = mulhi(b2, h - bh + 1), x0 = mulhi(b3, w - bw + 1); the box covers rows y0 .. y0 + bh - 1, columns x0 ..
+ * x0 + bw - 1.  A caller advances offset by ceil(n*h*w*c / 4) per call as for svae_op_make_batch; h*w*c >= 4 makes
+ * that at least n, so consecutive calls share no image counter.  The result depends on the arguments alone: on no
+ * launch geometry, not on the kernel chosen (LDS bands, or global memory when a band of 8 rows plus halos exceeds
+ * 64 KB) and not on the alignment path; two calls give the same bytes.
+ * SVAE_EBADARG (checked on the host before any launch): null target, input or spec; input == target (the blur reads
+ * neighbours); n, h, w or c <= 0; h*w*c < 4; a probability outside [0, 1]; sigma_lo < 0, sigma_lo > sigma_hi or
+ * sigma_hi > 4; factor not in {1, 2, 4, 8}; boxes outside 0 .. 4; min_side < 1 or min_side > max_side; a negative
+ * gaussian_scale; lo > hi.  SVAE_EBADCONFIG: h*w*c > 2^31 - 1. */
+typedef struct svae_degrade_spec {
+  float p_blur, sigma_lo, sigma_hi;      /* Gaussian blur, sigma uniform in [lo, hi], hi <= 4 */
+  float p_down; int32_t factor;          /* box down-sample by factor in {1,2,4,8}, replicated back */
+  float p_cut;  int32_t boxes, min_side, max_side; float fill;   /* boxes in 0..4 */
+  float pepper_prob, salt_prob, gaussian_scale;                  /* make_batch's pixel noise */
+} svae_degrade_spec;
+int svae_op_degrade_batch(const float* target, int n, int h, int w, int c, float lo, float hi,
+                          const svae_degrade_spec* spec, uint64_t seed, uint64_t offset, float* input, float* mask,
+                          void* stream);
+
 /* Segmented statistics of one fp32 device array in one pass (no reference counterpart; the numbers behind
  * the training summaries).  Segments (offset, length) in elements of x: disjoint, ascending, gaps allowed,
  * any alignment, length 0 legal.  With y = clamp(x, -c, +c) (c = +inf: none), row s of out [n_seg][8] (fp64):

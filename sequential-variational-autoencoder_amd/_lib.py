@@ -42,6 +42,15 @@ class SvaeConfig(ctypes.Structure):
     ]
 
 
+class SvaeDegradeSpec(ctypes.Structure):
+    """svae_degrade_spec (include/svae_hip.h)."""
+    _fields_ = [("p_blur", ctypes.c_float), ("sigma_lo", ctypes.c_float), ("sigma_hi", ctypes.c_float),
+                ("p_down", ctypes.c_float), ("factor", ctypes.c_int32),
+                ("p_cut", ctypes.c_float), ("boxes", ctypes.c_int32), ("min_side", ctypes.c_int32),
+                ("max_side", ctypes.c_int32), ("fill", ctypes.c_float),
+                ("pepper_prob", ctypes.c_float), ("salt_prob", ctypes.c_float), ("gaussian_scale", ctypes.c_float)]
+
+
 class SvaeParamDesc(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 96), ("ndim", ctypes.c_int32), ("shape", ctypes.c_int32 * 4),
                 ("offset", ctypes.c_int64), ("init", ctypes.c_int32), ("flags", ctypes.c_int32)]
@@ -141,6 +150,8 @@ def _load(path):
         "svae_op_dense_bf16": ([vp, i32, i32, vp, i32, i32, vp, vp, i64, ctypes.POINTER(i32), vp], i32),
         "svae_op_fc_wgrad": ([vp, i32, i32, vp, i32, i32, vp, vp], i32),
         "svae_op_make_batch": ([vp, i32, vp, i64, i32, i64, f32, f32, f32, f32, f32, u64, u64, vp, vp, vp], i32),
+        "svae_op_degrade_batch": ([vp, i32, i32, i32, i32, f32, f32, ctypes.POINTER(SvaeDegradeSpec), u64, u64, vp, vp,
+                                   vp], i32),
         "svae_op_stats_plan": ([ctypes.POINTER(i64), ctypes.POINTER(i64), i32, ctypes.POINTER(i64), i64], i64),
         "svae_op_tensor_stats": ([vp, vp, i32, i64, f32, vp, vp, vp], i32),
         "svae_op_image_metrics": ([vp, i32, vp, i32, i32, i32, i32, f32, vp, vp], i32),
@@ -237,7 +248,8 @@ EXPORTED = ["svae_param_count", "svae_param_layout", "svae_create", "svae_destro
             "svae_op_latent_fwd", "svae_op_latent_bwd", "svae_op_heads_bwd", "svae_op_splitfc",
             "svae_op_splitfc_bwd", "svae_op_stats_plan", "svae_op_tensor_stats", "svae_op_wgrad_last_kernel",
             "svae_op_dense_bf16", "svae_op_fc_wgrad", "svae_op_image_metrics",
-            "svae_op_mixture_logdensity", "svae_op_pairwise_scratch_bytes", "svae_op_pairwise_stats"]
+            "svae_op_mixture_logdensity", "svae_op_pairwise_scratch_bytes", "svae_op_pairwise_stats",
+            "svae_op_degrade_batch"]
 # include/svae_pcnn.h (the PixelCNN++ head)
 PCNN_EXPORTED = ["svae_pcnn_wnorm", "svae_pcnn_wnorm_bwd", "svae_pcnn_conv", "svae_pcnn_conv_wgrad", "svae_pcnn_colsum",
                  "svae_pcnn_colsum_absmax", "svae_pcnn_im2col_h16", "svae_pcnn_conv_planes_amax",

@@ -9,6 +9,7 @@
 #include <cstdint>
 
 #include "common.h"
+#include "corrupt.h"
 #include "kernels.h"
 #include "philox.h"
 
@@ -16,40 +17,6 @@ namespace {
 
 constexpr int MB_THREADS = 256;
 constexpr int MB_TILE = MB_THREADS * 16;  // elements of one uint8 tile: one 16-byte load per lane
-
-// the four outputs of group g from its four clean values
-__device__ __forceinline__ void mb_corrupt(const float t[4], long long g, const MakeBatchArgs& a, float o[4]) {
-#pragma clang fp contract(off)
-  const unsigned long long ctr = a.offset + (unsigned long long)g;
-  const unsigned lo32 = (unsigned)ctr, hi32 = (unsigned)(ctr >> 32);
-  const unsigned k0 = (unsigned)a.seed, k1 = (unsigned)(a.seed >> 32);
-  float nrm[4] = {0.f, 0.f, 0.f, 0.f};
-  unsigned pw[4] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};  // keep (thr_pepper = 0: every word keeps)
-  unsigned sw[4] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};  // no salt (thr_salt = 0: no word salts)
-  if (a.scale != 0.f) {  // the normals are finite, so a zero scale adds exactly +-0
-    unsigned c0 = lo32, c1 = hi32, c2 = 0, c3 = 0;
-    philox(c0, c1, c2, c3, k0, k1);
-    philox_box_muller(c0, c1, c2, c3, nrm);
-  }
-  if (a.thr_pepper) {
-    pw[0] = lo32; pw[1] = hi32; pw[2] = 1; pw[3] = 0;
-    philox(pw[0], pw[1], pw[2], pw[3], k0, k1);
-  }
-  if (a.thr_salt) {
-    sw[0] = lo32; sw[1] = hi32; sw[2] = 2; sw[3] = 0;
-    philox(sw[0], sw[1], sw[2], sw[3], k0, k1);
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float keep = pw[j] >= a.thr_pepper ? 1.f : 0.f;
-    const float salt = sw[j] < a.thr_salt ? 1.f : 0.f;
-    // each operation rounded on its own (contract(off) above), in the order the contract states
-    float v = t[j] * keep + salt;
-    const float gn = a.scale * nrm[j];
-    v = v + gn;
-    o[j] = fminf(fmaxf(v, a.lo), a.hi);
-  }
-}
 
 // lo + q * qscale with the product and the sum each rounded to fp32 (the *_rn intrinsics are plain operators
 // to the compiler, which would contract them into one fma: the pragma keeps the two roundings the contract states)

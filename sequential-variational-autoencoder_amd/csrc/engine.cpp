@@ -3778,6 +3778,45 @@ int svae_op_make_batch(const void* data, int data_u8, const int32_t* idx, int64_
   return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
 }
 
+int svae_op_degrade_batch(const float* target, int n, int h, int w, int c, float lo, float hi,
+                          const svae_degrade_spec* spec, uint64_t seed, uint64_t offset, float* input, float* mask,
+                          void* stream) {
+  if (!target || !input || !spec) return fail(nullptr, SVAE_EBADARG, "degrade_batch: null target, input or spec");
+  if (input == target) return fail(nullptr, SVAE_EBADARG, "degrade_batch: in place is not possible (the blur reads neighbours)");
+  if (n <= 0 || h <= 0 || w <= 0 || c <= 0) return fail(nullptr, SVAE_EBADARG, "degrade_batch: n, h, w and c must be positive");
+  const int64_t per_image = (int64_t)h * w * c;
+  if (per_image < 4) return fail(nullptr, SVAE_EBADARG, "degrade_batch: h * w * c must be at least 4");
+  if (per_image > 2147483647LL) return fail(nullptr, SVAE_EBADCONFIG, "degrade_batch: at most 2^31 - 1 elements per image");
+  const svae_degrade_spec& p = *spec;
+  auto prob = [](float v) { return v >= 0.f && v <= 1.f; };
+  if (!prob(p.p_blur) || !prob(p.p_down) || !prob(p.p_cut) || !prob(p.pepper_prob) || !prob(p.salt_prob))
+    return fail(nullptr, SVAE_EBADARG, "degrade_batch: a probability outside [0, 1]");
+  if (!(p.sigma_lo >= 0.f) || !(p.sigma_lo <= p.sigma_hi) || !(p.sigma_hi <= 4.f))
+    return fail(nullptr, SVAE_EBADARG, "degrade_batch: need 0 <= sigma_lo <= sigma_hi <= 4");
+  if (p.factor != 1 && p.factor != 2 && p.factor != 4 && p.factor != 8)
+    return fail(nullptr, SVAE_EBADARG, "degrade_batch: factor must be 1, 2, 4 or 8");
+  if (p.boxes < 0 || p.boxes > 4) return fail(nullptr, SVAE_EBADARG, "degrade_batch: boxes must be in 0 .. 4");
+  if (p.min_side < 1 || p.min_side > p.max_side)
+    return fail(nullptr, SVAE_EBADARG, "degrade_batch: need 1 <= min_side <= max_side");
+  if (!(p.gaussian_scale >= 0.f)) return fail(nullptr, SVAE_EBADARG, "degrade_batch: negative gaussian_scale");
+  if (!(lo <= hi)) return fail(nullptr, SVAE_EBADARG, "degrade_batch: lo > hi");
+  DegradeArgs a{};
+  a.target = target; a.input = input; a.mask = mask;
+  a.n = n; a.h = h; a.w = w; a.c = c;
+  a.thr_blur = prob_threshold(p.p_blur); a.thr_down = prob_threshold(p.p_down); a.thr_cut = prob_threshold(p.p_cut);
+  a.sigma_lo = p.sigma_lo; a.sigma_hi = p.sigma_hi; a.fill = p.fill;
+  a.factor = p.factor; a.boxes = p.boxes; a.min_side = p.min_side; a.max_side = p.max_side;
+  // the largest tap radius a draw can give: sigma <= sigma_hi, and the kernel forms ceilf(3.f * sigma) alike
+  const int rmax = (int)std::ceil(3.f * p.sigma_hi);
+  a.rmax = a.thr_blur ? (rmax < 12 ? rmax : 12) : 0;
+  a.nz.lo = lo; a.nz.hi = hi; a.nz.scale = p.gaussian_scale;
+  a.nz.thr_pepper = prob_threshold(p.pepper_prob); a.nz.thr_salt = prob_threshold(p.salt_prob);
+  a.nz.seed = seed; a.nz.offset = offset;
+  degrade_batch(a, (hipStream_t)stream);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
+}
+
 int64_t svae_op_stats_plan(const int64_t* offsets, const int64_t* lengths, int32_t n_seg, int64_t* table,
                            int64_t cap_words) {
   if (n_seg < 0 || (n_seg > 0 && (!offsets || !lengths)) || cap_words < 0)

@@ -350,6 +350,22 @@ struct MakeBatchArgs {
   float* target; float* input;       // either may be nullptr
 };
 void make_batch(const MakeBatchArgs& a, hipStream_t s);
+// ---- structured corruptions (degrade.hip): blur, box down-sampling, cut-out, then make_batch's pixel noise ----
+// target [n,h,w,c] -> input (and mask [n,h,w], may be nullptr), one launch.  Per-image draws: Philox counter
+// (offset + b, c2 = 3, c3 = block): block 0 the three gates and sigma, block 1 + k box k.  nz carries the pixel noise
+// (lo, hi, scale, thr_pepper, thr_salt, seed, offset: the fields mb_corrupt reads).
+struct DegradeArgs {
+  const float* target; float* input; float* mask;
+  int n, h, w, c;
+  unsigned thr_blur, thr_down, thr_cut;
+  float sigma_lo, sigma_hi, fill;
+  int factor, boxes, min_side, max_side;
+  int rmax;                          // min(ceil(3 sigma_hi), 12), 0 without blur: what the LDS band is sized for
+  MakeBatchArgs nz;
+};
+// bytes of LDS the band kernel needs for bands of `band` rows (degrade_batch falls back to global memory above 64 KB)
+long long degrade_lds_bytes(const DegradeArgs& a, int band);
+void degrade_batch(const DegradeArgs& a, hipStream_t s);
 // ---- segmented statistics (stats.hip): the eight fp64 columns of svae_op_tensor_stats per segment ----
 // plan table (int64 words): [0, n_seg] the index of every segment's first chunk (entry n_seg = n_chunks), then
 // per chunk (begin, segment << 32 | length).  stats_plan returns the chunk count (table == nullptr: count only),

@@ -9,6 +9,11 @@ the returned loss.
 Draws are counter-based (Philox, key = seed, counter = offset): training noise and test noise use
 different seeds, each offset advances by ceil(B H W C / 4) per corrupted batch, and both are part of
 state_dict(), so a resumed run corrupts its next batch exactly as the uninterrupted run would.
+
+With ``degradation`` (a degrade.Degradation) the input is instead the clean target blurred, down-sampled and cut
+out per image by svae_op_degrade_batch (csrc/degrade.hip), a second enqueue after a target-only make_batch, under
+the same seeds and offsets (its per-image draws come from a Philox stream make_batch leaves unused), followed by
+the pixel noise above when denoise_train is on.  No new state: state_dict() is what it was.
 """
 import json
 import logging
@@ -36,7 +41,7 @@ class NoisyTrainer:
 
     def __init__(self, network, dataset, denoise_train=False, vis_frequency=1000, plot_reconstruction=False,
                  base_dir=None, logger=None, seed=0, summary_freq=0, eval_frequency=0, info_frequency=0,
-                 quality_frequency=0):
+                 quality_frequency=0, degradation=None):
         if list(dataset.data_dims) != list(network.data_dims):
             raise ValueError("dataset images %s, network %s" % (dataset.data_dims, network.data_dims))
         if tuple(dataset.range) != tuple(float(v) for v in network.cfg.range):
@@ -46,6 +51,10 @@ class NoisyTrainer:
         self.network = network
         self.dataset = dataset
         self.denoise_train = bool(denoise_train)
+        # a degrade.Degradation: every training, test and evaluation input is the clean batch blurred, down-sampled
+        # and cut out by svae_op_degrade_batch (csrc/degrade.hip), then given the pixel noise (under denoise_train);
+        # None: every launch is exactly what it is without this option
+        self.degradation = degradation
         self.vis_frequency = int(vis_frequency)
         self.plot_reconstruction_enabled = bool(plot_reconstruction)
         self.base_dir = base_dir
@@ -90,6 +99,26 @@ class NoisyTrainer:
             self.dataset.per_image, lo, hi, p, s, g, seed, offset & 0xFFFFFFFFFFFFFFFF, _lib.ptr(target),
             _lib.ptr(inp), _lib.stream_ptr(torch.cuda.current_stream(self.device))))
 
+    def _corrupted_batch(self, data, start, seed, offset):
+        """The window [start, start + B) of ``data`` as the clean self._target and the network's input; returns
+        (input, corrupted).  Without a degradation and without denoise_train the input is the target itself and
+        no draw is made (corrupted is False: the caller leaves its offset alone).  With denoise_train alone it is
+        svae_op_make_batch's noisy copy under (seed, offset).  With a degradation it is svae_op_degrade_batch of
+        the clean target under the same (seed, offset), the pixel noise being the class constants under
+        denoise_train and zero otherwise.  A corrupting call consumes ceil(B H W C / 4) counters."""
+        if self.degradation is None:
+            if not self.denoise_train:
+                self._make_batch(data, start, self._target, None, 0, 0, noise=False)
+                return self._target, False
+            self._make_batch(data, start, self._target, self._input, seed, offset)
+            return self._input, True
+        from . import degrade
+        self._make_batch(data, start, self._target, None, 0, 0, noise=False)
+        lo, hi = self.dataset.range
+        noise = (self.pepper_prob, self.salt_prob, self.gaussian_noise_scale) if self.denoise_train else (0.0, 0.0, 0.0)
+        degrade.degrade_batch(self._target, self.degradation, lo, hi, noise, seed, offset, out=self._input)
+        return self._input, True
+
     def apply_noise(self, batch):
         """The reference's apply_noise on a given fp32 device batch [B,H,W,C], in place (the same kernel
         with input == data); draws from the training stream.  Raises when denoise_train is off, as the
@@ -109,16 +138,13 @@ class NoisyTrainer:
         ds = self.dataset
         start, _ = ds.next_test_batch(self.batch_size) if test else ds.next_batch(self.batch_size)
         data = ds.test if test else ds.train
-        if not self.denoise_train:
-            self._make_batch(data, start, self._target, None, 0, 0, noise=False)
-            return self._target, self._target
         if test:
-            self._make_batch(data, start, self._target, self._input, self.seed ^ self.test_seed_xor, self.test_offset)
-            self.test_offset += self._groups()
+            inp, corrupted = self._corrupted_batch(data, start, self.seed ^ self.test_seed_xor, self.test_offset)
+            self.test_offset += self._groups() if corrupted else 0
         else:
-            self._make_batch(data, start, self._target, self._input, self.seed, self.train_offset)
-            self.train_offset += self._groups()
-        return self._input, self._target
+            inp, corrupted = self._corrupted_batch(data, start, self.seed, self.train_offset)
+            self.train_offset += self._groups() if corrupted else 0
+        return inp, self._target
 
     # ------------------------------------------------------------------ the reference's loop
     def step(self):
@@ -201,7 +227,8 @@ class NoisyTrainer:
         windows.  Nothing of the training run moves: not the dataset cursors, not train_offset / test_offset,
         not the parameters, the Adam state or the iteration, and not the network's device Philox counter,
         because every draw is injected.  With denoise_train the corruption is svae_op_make_batch under the key
-        ``seed ^ eval_seed_xor`` from offset 0 (advancing by one batch per window); eps [T,B,Dz] and then, under
+        ``seed ^ eval_seed_xor`` from offset 0 (advancing by one batch per window), with a ``degradation``
+        svae_op_degrade_batch under the same key and offsets (_corrupted_batch); eps [T,B,Dz] and then, under
         add_noise_to_chain, the chain noise [T,B,H,W,C] of every window come from one
         ``torch.Generator(device).manual_seed(seed)`` made at the start.  ``seed`` defaults to the trainer's.
         Every evaluation of a split therefore scores the same corrupted images with the same draws.
@@ -253,13 +280,8 @@ class NoisyTrainer:
         stream = _lib.stream_ptr(torch.cuda.current_stream(self.device))
         offset = 0
         for start, fresh in windows:
-            if self.denoise_train:
-                self._make_batch(data, start, self._target, self._input, seed ^ self.eval_seed_xor, offset)
-                offset += self._groups()
-                inp = self._input
-            else:
-                self._make_batch(data, start, self._target, None, 0, 0, noise=False)
-                inp = self._target
+            inp, corrupted = self._corrupted_batch(data, start, seed ^ self.eval_seed_xor, offset)
+            offset += self._groups() if corrupted else 0
             eps = torch.randn([T, B, net.cfg.latent_dim], generator=gen, dtype=torch.float32, device=self.device)
             noise = None
             if net.cfg.add_noise_to_chain:
@@ -350,13 +372,8 @@ class NoisyTrainer:
         kept = torch.empty([3, T, images, Dz], dtype=torch.float32, device=self.device)  # mu, sigma, z
         offset = done = 0
         for start, fresh in windows:
-            if self.denoise_train:
-                self._make_batch(data, start, self._target, self._input, seed ^ self.eval_seed_xor, offset)
-                offset += self._groups()
-                inp = self._input
-            else:
-                self._make_batch(data, start, self._target, None, 0, 0, noise=False)
-                inp = self._target
+            inp, corrupted = self._corrupted_batch(data, start, seed ^ self.eval_seed_xor, offset)
+            offset += self._groups() if corrupted else 0
             eps = torch.randn([T, B, Dz], generator=gen, dtype=torch.float32, device=self.device)
             noise = None
             if net.cfg.add_noise_to_chain:

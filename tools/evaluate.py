@@ -43,8 +43,14 @@ def parse(argv=None):
                          "two-sample accuracy and nearest-training-image distances of generated samples against the "
                          "split's whole windows; written to sample_quality.json")
     ap.add_argument("--dtype", default="bf16x6", choices=["fp32", "bf16", "bf16x6"])
+    importlib.import_module(PKG + ".degrade").add_flags(ap)
     ap.add_argument("--models_dir", default="models")
     return ap.parse_args(argv)
+
+
+def degradation(a):
+    """The Degradation --blur, --downsample and --cutout name (None: none of them given)."""
+    return importlib.import_module(PKG + ".degrade").Degradation.from_flags(a.blur, a.downsample, a.cutout)
 
 
 def main(argv=None):
@@ -80,7 +86,7 @@ def main(argv=None):
     net = SV(cfg, seed=run_seed)
     net.name = a.netname
     net.load_checkpoint(ckpt)
-    trainer = NT(net, ds, denoise_train=a.denoise_train, seed=run_seed)
+    trainer = NT(net, ds, denoise_train=a.denoise_train, seed=run_seed, degradation=degradation(a))
     row = {"iteration": int(state.get("iteration", net.iteration))}
     if a.latent_information and a.sample_quality:
         print("--latent_information and --sample_quality are two reports: ask for one")

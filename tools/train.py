@@ -47,6 +47,7 @@ def parse(argv=None):
                          "samples) to <model dir>/sample_quality.jsonl every N iterations (0: off)")
     ap.add_argument("--iters", type=int, default=None, help="iterations to run (default: the reference's 10^7)")
     ap.add_argument("--dtype", default="bf16x6", choices=["fp32", "bf16", "bf16x6"])
+    importlib.import_module(PKG + ".degrade").add_flags(ap)
     ap.add_argument("--models_dir", default="models")
     ap.add_argument("--seed", type=int, default=0)
     return ap.parse_args(argv)
@@ -59,6 +60,11 @@ def model_dir_error(base_dir, continue_training):
     if os.path.isdir(base_dir) and not continue_training:
         return "Model already exists. Either use a new version number, or, set the --continue_training flag"
     return None
+
+
+def degradation(a):
+    """The Degradation --blur, --downsample and --cutout name (None: none of them given)."""
+    return importlib.import_module(PKG + ".degrade").Degradation.from_flags(a.blur, a.downsample, a.cutout)
 
 
 def main(argv=None):
@@ -93,7 +99,8 @@ def main(argv=None):
     trainer = NT(net, ds, denoise_train=a.denoise_train, vis_frequency=a.vis_frequency,
                  plot_reconstruction=a.plot_reconstruction, base_dir=base_dir, logger=log, seed=a.seed,
                  summary_freq=a.summary_freq, eval_frequency=a.eval_frequency,
-                 info_frequency=a.info_frequency, quality_frequency=a.quality_frequency)
+                 info_frequency=a.info_frequency, quality_frequency=a.quality_frequency,
+                 degradation=degradation(a))
     if a.continue_training and os.path.exists(os.path.join(base_dir, "trainer.json")):
         trainer.load(base_dir)
         log.info("resumed at iteration %d" % trainer.iteration)
