@@ -416,6 +416,48 @@ int svae_op_degrade_batch(const float* target, int n, int h, int w, int c, float
                           const svae_degrade_spec* spec, uint64_t seed, uint64_t offset, float* input, float* mask,
                           void* stream);
 
+/* Overlapping tiles: the work around the forward when a network of tile size th x tw restores whole images (no
+ * reference counterpart).  Both ops are one launch on `stream`, no allocation, no synchronisation, no atomics: the
+ * result depends on the arguments alone (on no launch geometry, not on the alignment path or the kernel variant),
+ * and two calls give the same bytes.
+ * Geometry, per axis with image extent L, tile extent t <= L and stride 1 <= s <= t: k = ceil((L - t) / s) + 1
+ * tiles, tile i at o_i = min(i s, L - t) (the last tile is pulled back to the edge: nothing is padded).  Tile
+ * (m, i, j) of image m, row tile i, column tile j has id (m k_y + i) k_x + j; n_tiles = nimg k_y k_x.  The window
+ * weight of tile pixel (p, q) is w1_y(p) w1_x(q) with w1(p) = min(p + 1, t - p), a small exact integer.
+ *
+ * svae_op_extract_tiles: images [nimg,H,W,c] (uint8 when data_u8 = 1, else fp32, any base alignment) -> tiles
+ * [count,th,tw,c] fp32.  Row r receives tile (first + r) mod n_tiles; count > n_tiles is legal and wraps.  A uint8
+ * pixel q becomes lo + q * ((hi - lo) / 255) exactly as in svae_op_make_batch (the product and the sum each rounded
+ * to fp32); fp32 pixels are copied as they are.
+ *
+ * svae_op_blend_tiles: tiles holds nstack sets of all n_tiles tiles in id order, set k at tiles + k * stack_stride
+ * floats; out [nstack,nimg,H,W,c] fp32 and out_u8 of the same shape in uint8, either may be NULL, not both.
+ * Output element (k, m, y, x, ch):
+ *   acc = sum_i sum_j (double)(w1_y(y - oy_i) * w1_x(x - ox_j)) * (double)tile value   over the covering tiles,
+ *         i ascending outside, j ascending inside, from 0, every product and sum in fp64
+ *   Wgt = sum_i sum_j of the same weights (an exact integer)
+ *   v   = (float)(acc / Wgt)             one IEEE fp64 division, one rounding to fp32
+ * The tiles covering a position of an axis form one contiguous index range (origins are non-decreasing; the
+ * clamped last tile is an ordinary member).  Where known [nimg,H,W] (uint8, may be NULL) is non-zero at (m, y, x),
+ * v is instead the source pixel at (m, y, x, ch) in every stack: source has the layout of images (uint8 when
+ * source_u8 = 1, dequantised as above; else fp32 as it is) and is required when and only when known is given.
+ *   out_u8 = (uint8) min(max(rintf((v - lo) * (255 / (hi - lo))), 0), 255)
+ * with the constant 255 / (hi - lo) rounded to fp32 and the difference and the product each rounded to fp32.
+ * Two consequences:
+ *   (a) where every covering tile carries the same value u (and Wgt < 2^29, which SVAE_EBADCONFIG enforces) every
+ *       partial sum is exact and v == u bit for bit: blend(extract(img)) == img bitwise for fp32 images;
+ *   (b) for uint8 images, extract followed by blend into out_u8 returns the input bytes.
+ * SVAE_EBADARG (checked on the host before any device call): null images or tiles, out and out_u8 both null; known
+ * without source or source without known; nimg, H, W, c, th, tw, sy, sx, count or nstack <= 0; th > H, tw > W,
+ * sy > th or sx > tw; first < 0 or first >= n_tiles; stack_stride < n_tiles*th*tw*c; lo >= hi where a uint8 side
+ * (images, source or out_u8) is involved.  SVAE_EBADCONFIG: th*tw*c or H*W*c > 2^31 - 1; (blend) the largest
+ * per-axis weight sums have a product of 2^29 or more. */
+int svae_op_extract_tiles(const void* images, int data_u8, int nimg, int H, int W, int c, int th, int tw, int sy,
+                          int sx, float lo, float hi, int64_t first, int64_t count, float* tiles, void* stream);
+int svae_op_blend_tiles(const float* tiles, int nstack, int64_t stack_stride, int nimg, int H, int W, int c, int th,
+                        int tw, int sy, int sx, const void* source, int source_u8, const uint8_t* known, float lo,
+                        float hi, float* out, uint8_t* out_u8, void* stream);
+
 /* Segmented statistics of one fp32 device array in one pass (no reference counterpart; the numbers behind
  * the training summaries).  Segments (offset, length) in elements of x: disjoint, ascending, gaps allowed,
  * any alignment, length 0 legal.  With y = clamp(x, -c, +c) (c = +inf: none), row s of out [n_seg][8] (fp64):

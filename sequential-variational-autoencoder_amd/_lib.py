@@ -152,6 +152,9 @@ def _load(path):
         "svae_op_make_batch": ([vp, i32, vp, i64, i32, i64, f32, f32, f32, f32, f32, u64, u64, vp, vp, vp], i32),
         "svae_op_degrade_batch": ([vp, i32, i32, i32, i32, f32, f32, ctypes.POINTER(SvaeDegradeSpec), u64, u64, vp, vp,
                                    vp], i32),
+        "svae_op_extract_tiles": ([vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, f32, i64, i64, vp, vp], i32),
+        "svae_op_blend_tiles": ([vp, i32, i64, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, f32, f32, vp, vp,
+                                 vp], i32),
         "svae_op_stats_plan": ([ctypes.POINTER(i64), ctypes.POINTER(i64), i32, ctypes.POINTER(i64), i64], i64),
         "svae_op_tensor_stats": ([vp, vp, i32, i64, f32, vp, vp, vp], i32),
         "svae_op_image_metrics": ([vp, i32, vp, i32, i32, i32, i32, f32, vp, vp], i32),
@@ -249,7 +252,7 @@ EXPORTED = ["svae_param_count", "svae_param_layout", "svae_create", "svae_destro
             "svae_op_splitfc_bwd", "svae_op_stats_plan", "svae_op_tensor_stats", "svae_op_wgrad_last_kernel",
             "svae_op_dense_bf16", "svae_op_fc_wgrad", "svae_op_image_metrics",
             "svae_op_mixture_logdensity", "svae_op_pairwise_scratch_bytes", "svae_op_pairwise_stats",
-            "svae_op_degrade_batch"]
+            "svae_op_degrade_batch", "svae_op_extract_tiles", "svae_op_blend_tiles"]
 # include/svae_pcnn.h (the PixelCNN++ head)
 PCNN_EXPORTED = ["svae_pcnn_wnorm", "svae_pcnn_wnorm_bwd", "svae_pcnn_conv", "svae_pcnn_conv_wgrad", "svae_pcnn_colsum",
                  "svae_pcnn_colsum_absmax", "svae_pcnn_im2col_h16", "svae_pcnn_conv_planes_amax",

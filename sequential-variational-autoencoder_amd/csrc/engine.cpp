@@ -3817,6 +3817,95 @@ int svae_op_degrade_batch(const float* target, int n, int h, int w, int c, float
   return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
 }
 
+// ---- overlapping tiles (tiles.hip) ----
+static int tile_count(int L, int t, int s) { return (int)(((int64_t)L - t + s - 1) / s) + 1; }
+
+// the largest sum of window weights w1(p) = min(p + 1, t - p) over the tiles covering one position of an axis
+// (exact = false: an upper bound in O(1): at most ceil(t / s) + 1 tiles cover a position, each with at most ceil(t / 2))
+static int64_t tile_axis_weight(int L, int t, int s, bool exact) {
+  const int k = tile_count(L, t, s);
+  if (!exact) return std::min<int64_t>(k, ((int64_t)t + s - 1) / s + 1) * (((int64_t)t + 1) / 2);
+  int64_t best = 0;
+  for (int64_t x = 0; x < L; ++x) {
+    int64_t hi = x >= (int64_t)L - t ? k - 1 : x / s, lo = x < t ? 0 : (x - t) / s + 1, sum = 0;
+    if (lo > k - 1) lo = k - 1;
+    for (int64_t i = lo; i <= hi; ++i) {
+      const int64_t p = x - std::min<int64_t>(i * s, (int64_t)L - t);
+      sum += std::min<int64_t>(p + 1, t - p);
+    }
+    best = std::max(best, sum);
+  }
+  return best;
+}
+
+// the checks the two tile ops share; fills g.  0, or the code fail() returned
+static int tile_geometry(const char* op, int nimg, int H, int W, int c, int th, int tw, int sy, int sx, TileGeom& g) {
+  const std::string who(op);
+  if (nimg <= 0 || H <= 0 || W <= 0 || c <= 0 || th <= 0 || tw <= 0 || sy <= 0 || sx <= 0)
+    return fail(nullptr, SVAE_EBADARG, who + ": nimg, H, W, c, th, tw, sy and sx must be positive");
+  if (th > H || tw > W) return fail(nullptr, SVAE_EBADARG, who + ": the tile exceeds the image");
+  if (sy > th || sx > tw) return fail(nullptr, SVAE_EBADARG, who + ": the stride exceeds the tile");
+  g.nimg = nimg; g.H = H; g.W = W; g.c = c; g.th = th; g.tw = tw; g.sy = sy; g.sx = sx;
+  g.ky = tile_count(H, th, sy); g.kx = tile_count(W, tw, sx);
+  g.n_tiles = (long long)nimg * g.ky * g.kx;
+  return 0;
+}
+
+static int tile_sizes(const char* op, const TileGeom& g) {
+  if ((int64_t)g.th * g.tw * g.c > 2147483647LL || (int64_t)g.H * g.W * g.c > 2147483647LL)
+    return fail(nullptr, SVAE_EBADCONFIG, std::string(op) + ": at most 2^31 - 1 elements per tile and per image");
+  return 0;
+}
+
+int svae_op_extract_tiles(const void* images, int data_u8, int nimg, int H, int W, int c, int th, int tw, int sy,
+                          int sx, float lo, float hi, int64_t first, int64_t count, float* tiles, void* stream) {
+  if (!images || !tiles) return fail(nullptr, SVAE_EBADARG, "extract_tiles: null images or tiles");
+  ExtractTilesArgs a{};
+  if (int rc = tile_geometry("extract_tiles", nimg, H, W, c, th, tw, sy, sx, a.g)) return rc;
+  if (count <= 0) return fail(nullptr, SVAE_EBADARG, "extract_tiles: count must be positive");
+  if (first < 0 || first >= a.g.n_tiles)
+    return fail(nullptr, SVAE_EBADARG, "extract_tiles: first must be in [0, n_tiles)");
+  if (data_u8 && !(lo < hi)) return fail(nullptr, SVAE_EBADARG, "extract_tiles: lo >= hi with uint8 images");
+  if (int rc = tile_sizes("extract_tiles", a.g)) return rc;
+  a.images = images; a.data_u8 = data_u8 ? 1 : 0;
+  a.lo = lo; a.qscale = (float)(((double)hi - (double)lo) / 255.0);
+  a.first = first; a.count = count; a.tiles = tiles;
+  extract_tiles(a, (hipStream_t)stream);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
+}
+
+int svae_op_blend_tiles(const float* tiles, int nstack, int64_t stack_stride, int nimg, int H, int W, int c, int th,
+                        int tw, int sy, int sx, const void* source, int source_u8, const uint8_t* known, float lo,
+                        float hi, float* out, uint8_t* out_u8, void* stream) {
+  if (!tiles) return fail(nullptr, SVAE_EBADARG, "blend_tiles: null tiles");
+  if (!out && !out_u8) return fail(nullptr, SVAE_EBADARG, "blend_tiles: out and out_u8 are both null");
+  if ((known != nullptr) != (source != nullptr))
+    return fail(nullptr, SVAE_EBADARG, "blend_tiles: known and source come together");
+  BlendTilesArgs a{};
+  if (int rc = tile_geometry("blend_tiles", nimg, H, W, c, th, tw, sy, sx, a.g)) return rc;
+  if (nstack <= 0) return fail(nullptr, SVAE_EBADARG, "blend_tiles: nstack must be positive");
+  if (stack_stride < 0 || (unsigned __int128)stack_stride < (unsigned __int128)a.g.n_tiles * th * tw * c)
+    return fail(nullptr, SVAE_EBADARG, "blend_tiles: stack_stride is smaller than a set of tiles");
+  if ((out_u8 || (source && source_u8)) && !(lo < hi))
+    return fail(nullptr, SVAE_EBADARG, "blend_tiles: lo >= hi with a uint8 source or output");
+  if (int rc = tile_sizes("blend_tiles", a.g)) return rc;
+  const auto reaches = [&](bool exact) {  // both factors < 2^31 * 2^30: the comparison is made in fp64
+    return (double)tile_axis_weight(H, th, sy, exact) * (double)tile_axis_weight(W, tw, sx, exact) >= 536870912.0;
+  };
+  if (reaches(false) && reaches(true))
+    return fail(nullptr, SVAE_EBADCONFIG, "blend_tiles: the weight sum of a pixel reaches 2^29");
+  a.tiles = tiles; a.nstack = nstack; a.stack_stride = stack_stride;
+  a.source = source; a.source_u8 = source_u8 ? 1 : 0; a.known = known;
+  a.lo = lo;
+  a.qscale = (float)(((double)hi - (double)lo) / 255.0);
+  a.qinv = (float)(255.0 / ((double)hi - (double)lo));
+  a.out = out; a.out_u8 = out_u8;
+  blend_tiles(a, (hipStream_t)stream);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
+}
+
 int64_t svae_op_stats_plan(const int64_t* offsets, const int64_t* lengths, int32_t n_seg, int64_t* table,
                            int64_t cap_words) {
   if (n_seg < 0 || (n_seg > 0 && (!offsets || !lengths)) || cap_words < 0)

@@ -366,6 +366,29 @@ struct DegradeArgs {
 // bytes of LDS the band kernel needs for bands of `band` rows (degrade_batch falls back to global memory above 64 KB)
 long long degrade_lds_bytes(const DegradeArgs& a, int band);
 void degrade_batch(const DegradeArgs& a, hipStream_t s);
+// ---- overlapping tiles (tiles.hip): svae_op_extract_tiles and svae_op_blend_tiles ----
+// per axis: k = ceil((L - t) / s) + 1 tiles, tile i at min(i s, L - t); tile id (m ky + i) kx + j
+struct TileGeom {
+  int nimg, H, W, c, th, tw, sy, sx;
+  int ky, kx;                        // tiles per axis
+  long long n_tiles;                 // nimg * ky * kx
+};
+struct ExtractTilesArgs {
+  TileGeom g;
+  const void* images; int data_u8;
+  float lo, qscale;                  // qscale = (hi - lo) / 255 rounded to fp32 (make_batch's)
+  long long first, count;
+  float* tiles;
+};
+struct BlendTilesArgs {
+  TileGeom g;
+  const float* tiles; int nstack; long long stack_stride;
+  const void* source; int source_u8; const unsigned char* known;   // source and known: both or neither
+  float lo, qscale, qinv;            // qinv = 255 / (hi - lo) rounded to fp32
+  float* out; unsigned char* out_u8; // either may be nullptr
+};
+void extract_tiles(const ExtractTilesArgs& a, hipStream_t s);
+void blend_tiles(const BlendTilesArgs& a, hipStream_t s);
 // ---- segmented statistics (stats.hip): the eight fp64 columns of svae_op_tensor_stats per segment ----
 // plan table (int64 words): [0, n_seg] the index of every segment's first chunk (entry n_seg = n_chunks), then
 // per chunk (begin, segment << 32 | length).  stats_plan returns the chunk count (table == nullptr: count only),

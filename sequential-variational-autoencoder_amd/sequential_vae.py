@@ -434,6 +434,42 @@ class SequentialVAE:
         self.forward(input_batch, input_batch, None, 1.0)
         return self.xhat(-1).cpu().numpy()
 
+    def restore(self, images, range=(-1.0, 1.0), stride=None, steps=-1, seed=None, known=None, as_uint8=None,
+                max_bytes=4 << 30):
+        """Apply the network to whole images of any size: overlapping tiles of the network's own h x w go through
+        the chain and are blended back with a triangular window (restore.py, csrc/tiles.hip).
+
+        ``images`` is [H,W,C] or [N,H,W,C] (C the network's), uint8 or float (floats already in ``range``), numpy
+        or torch.  ``stride`` (an int or a pair, default half the tile per axis) places the tiles; the last tile
+        of an axis is pulled back to the edge, nothing is padded.  An image smaller than the tile is
+        edge-replicated up to it and cropped afterwards.  ``steps`` is a chain step (negative: from the end) or
+        "all".  Returns a device tensor [N,H,W,C], or [T,N,H,W,C] for "all": uint8 (quantised from ``range``) if
+        ``as_uint8``, which defaults to the input being uint8, else float32.
+
+        ``known`` ([H,W] or [N,H,W], bool or uint8) marks pixels that come back exactly as given: the inpainting
+        use.  It is the complement of the ``mask`` svae_op_degrade_batch writes (1 where a pixel was cut out).
+
+        Tiles are walked in windows of the batch B as NoisyTrainer.evaluate() walks a split: first = 0, B, ...;
+        with a remainder the last window is [n_tiles - B, n_tiles), of which only the rows not yet produced are
+        kept; fewer than B tiles make one window that wraps around, so that a batch holds real tiles only.
+        BatchNorm runs on batch statistics, so a tile's output depends on its window
+        companions: the same image restored alone and among others differs slightly, and a lone tile-sized image
+        fills its window with B copies of itself, which leaves the batch statistics of the FC layers without
+        variance (restore several images, or a larger one, per call).  Per window: svae_op_extract_tiles into a kept input buffer,
+        forward(inp, inp, eps, 1.0, noise), x_hat of the requested steps into a kept [S, n_tiles, h, w, C]
+        buffer; then one svae_op_blend_tiles launch.  Above ``max_bytes`` of kept tiles a ValueError advises
+        fewer images per call.
+
+        ``seed`` = None restores with eps = 0, the posterior mean (and chain noise 0 under add_noise_to_chain):
+        deterministic.  ``seed`` = k draws eps and then the chain noise of every window from one
+        torch.Generator(device).manual_seed(k), as evaluate() does.  Every draw is injected, so nothing of a
+        training run moves: not the parameters, the Adam state or the iteration, and not the device Philox
+        counter.  Afterwards the network's last forward is the last window: summaries() reads the last forward,
+        so call it before restoring.  The PixelVAE head raises as in evaluate()."""
+        from . import restore as _restore
+        return _restore.restore(self, images, range=range, stride=stride, steps=steps, seed=seed, known=known,
+                                as_uint8=as_uint8, max_bytes=max_bytes)
+
     # ------------------------------------------------------------------ siblings / visualisation
     def _sync_shared(self):
         """A sibling reads parameters its owner's Adam writes behind this context's bf16 and shared-weight

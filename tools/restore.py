@@ -1,0 +1,83 @@
+"""Restore images of any size with a trained Sequential VAE (SequentialVAE.restore: overlapping tiles of the
+network's own size through the chain, blended back), from the checkpoint tools/train.py left in
+models/<netname>_v<version>.
+
+    python tools/restore.py --netname celeba --version 1 --input photo.npy --output restored.npy
+    python tools/restore.py --netname celeba --input damaged.npy --known intact.npy --output filled.npy --steps all
+
+--input is a .npy file [H,W,C] or [N,H,W,C], uint8 or float (floats already in --range); the output has the
+input's kind (uint8 in, uint8 out) and, with --steps all, a leading axis of chain steps.  --known is a .npy mask
+[H,W] or [N,H,W] (bool or uint8) of the pixels to give back untouched (inpainting).  Give --batch_size and --dtype
+the run was trained with.  Only .npy is read and written: there are no image decoders here.
+"""
+import argparse
+import importlib
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+PKG = "sequential-variational-autoencoder_amd"
+
+
+def parse(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--netname", default="celeba", help="a preset of config.py")
+    ap.add_argument("--version", type=int, default=1)
+    ap.add_argument("--input", required=True, help=".npy file, uint8 or float, [H,W,C] or [N,H,W,C]")
+    ap.add_argument("--output", required=True, help=".npy file to write")
+    ap.add_argument("--stride", type=int, default=None, help="tile stride in pixels (default: half the tile)")
+    ap.add_argument("--steps", default="-1", metavar="all|K", help="the chain step to return (default -1, the last) or all")
+    ap.add_argument("--seed", type=int, default=None, help="draw the latents from this seed (default: the posterior mean)")
+    ap.add_argument("--known", default=None, help=".npy mask of the pixels to give back as they are")
+    ap.add_argument("--range", default=None, metavar="LO,HI", help="the data range (default: the preset's)")
+    ap.add_argument("--batch_size", type=int, default=None, help="default: the preset's")
+    ap.add_argument("--dtype", default="bf16x6", choices=["fp32", "bf16", "bf16x6"])
+    ap.add_argument("--models_dir", default="models")
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    a = parse(argv)
+    for path in (a.input, a.output) + ((a.known,) if a.known else ()):
+        if not path.endswith(".npy"):
+            print("%s: only .npy files are read and written" % path)
+            return 1
+    base_dir = os.path.join(a.models_dir, "%s_v%d" % (a.netname, a.version))
+    ckpt = os.path.join(base_dir, "model.safetensors")
+    if not os.path.exists(ckpt):
+        print("no checkpoint at %s" % ckpt)
+        return 1
+    import json
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        print("tools/restore.py needs a GPU (the engine has no CPU path)")
+        return 1
+    cfgmod = importlib.import_module(PKG + ".config")
+    SV = importlib.import_module(PKG + ".sequential_vae").SequentialVAE
+    over = dict(dtype=a.dtype)
+    if a.batch_size:
+        over["batch"] = a.batch_size
+    cfg = cfgmod.preset(a.netname, **over)
+    state = {}
+    if os.path.exists(os.path.join(base_dir, "trainer.json")):
+        with open(os.path.join(base_dir, "trainer.json")) as f:
+            state = json.load(f)
+    net = SV(cfg, seed=int(state.get("seed", 0)))
+    net.name = a.netname
+    net.load_checkpoint(ckpt)
+    rng = tuple(float(v) for v in a.range.split(",")) if a.range else tuple(cfg.range)
+    if len(rng) != 2:
+        print("--range takes LO,HI")
+        return 1
+    steps = "all" if a.steps == "all" else int(a.steps)
+    known = np.load(a.known) if a.known else None
+    out = net.restore(np.load(a.input), range=rng, stride=a.stride, steps=steps, seed=a.seed, known=known)
+    np.save(a.output, out.cpu().numpy())
+    print("%s: %s %s" % (a.output, tuple(out.shape), str(out.dtype).replace("torch.", "")))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
