@@ -168,6 +168,10 @@ int svae_set_external_grads(svae_ctx* ctx, const float* dxhat, const float* dz);
  * tf.random_normal :1090-1091).  One-shot: every forward / generate call clears it, so a generative
  * chain never reuses the noise injected for an earlier training forward. */
 int svae_set_chain_noise(svae_ctx* ctx, const float* noise);
+/* The counter of the context's own Philox draws (eps, prior latents and chain noise drawn on the device when the
+ * caller passes none; every such draw advances it).  *get (may be NULL) receives the current value, then *set (may
+ * be NULL) replaces it: a checkpoint that carries it lets a resumed run draw what the uninterrupted run would. */
+int svae_rng_offset(svae_ctx* ctx, const uint64_t* set, uint64_t* get);
 /* Improvement-maximisation loss (add_improvement_maximization_loss): bind a caller-owned gradient
  * buffer (n_total elements, public layout), then after svae_forward, svae_backward_imp writes
  * d imp / d every variable into it (the optimiser uses only the recognition part, :1302).
@@ -415,6 +419,48 @@ typedef struct svae_degrade_spec {
 int svae_op_degrade_batch(const float* target, int n, int h, int w, int c, float lo, float hi,
                           const svae_degrade_spec* spec, uint64_t seed, uint64_t offset, float* input, float* mask,
                           void* stream);
+
+/* Random crops of large images as the clean batch, in one launch on `stream` (no allocation, no synchronisation, no
+ * atomics; no reference counterpart: the front of the restoration workflow, whose network of tile size h x w is
+ * trained on windows of images of any size H x W).  images [nimg,H,W,c] (uint8 when data_u8 = 1, else fp32, any base
+ * alignment) -> target [n,h,w,c] fp32 and target_u8 of the same shape in uint8; either may be NULL, not both, and
+ * target_u8 is legal only for uint8 images (it materialises fixed evaluation sets).  meta [n,5] int32 (may be NULL)
+ * receives (m, s, g, y0, x0) of every row.
+ * Row b with crops == NULL: draws are Philox4x32-10 under the key (lo32(seed), hi32(seed)) with the 64-bit value
+ * offset + b in the counter words (c0, c1), c2 = 4 (a stream neither svae_op_make_batch, 0 .. 2, nor
+ * svae_op_degrade_batch, 3, uses) and c3 = the block index; mulhi = the high 32 bits of the 32 x 32 product.
+ * Block 0 gives words a0..a3: image m = mulhi(a0, nimg), scale s = scales[mulhi(a1, n_scales)], symmetry
+ * g = mulhi(a2, symmetries).  Block 1 gives b0, b1: y0 = mulhi(b0, H - s*h + 1), x0 = mulhi(b1, W - s*w + 1).  A
+ * caller advances offset by at least n per call (the trainer advances it by ceil(n*h*w*c / 4), the step of the
+ * streams it shares the offset with).  With crops given ([n,5] int32 on the device) row b uses crops[b] =
+ * (m, s, g, y0, x0) as it is and nothing is drawn; values outside their ranges (m in [0, nimg), s in 1 .. 8 with
+ * s*h <= H and s*w <= W, g in [0, 8) and below 4 unless h == w, y0 in [0, H - s*h], x0 in [0, W - s*w]) are the
+ * caller's contract, as for svae_op_make_batch's idx: no device-side check.
+ * Symmetry g: bit 0 mirrors x, bit 1 mirrors y, bit 2 transposes.  For output pixel (i, j): (i', j') = (j, i) if
+ * bit 2 is set, else (i, j); then i' <- h - 1 - i' if bit 1 is set; then j' <- w - 1 - j' if bit 0 is set.
+ * symmetries = 2 yields g in {0, 1}, 4 yields {0 .. 3}, 8 yields {0 .. 7}.
+ * Output (b, i, j, ch) is the mean of the s x s source block at rows y0 + s*i' + p, columns x0 + s*j' + q of image m:
+ *   uint8   the exact integer sum; qbar = (float)sum / (float)(s*s), one correctly rounded fp32 division (s = 1:
+ *           none, qbar = the pixel); target = lo + qbar * ((hi - lo) / 255) with the constant, the product and the
+ *           sum each rounded to fp32, word for word svae_op_make_batch's dequantisation;
+ *           target_u8 = min(255, rintf(qbar)) (ties to even)
+ *   fp32    sequential fp32 adds from 0 in row-major order (p outside, q inside), then one correctly rounded fp32
+ *           division by s*s; s = 1 is a copy of the pixel
+ * Consequences: for s = 1, g = 0 the row equals svae_op_make_batch on the pre-cut tile, bit for bit.  The result
+ * depends on the arguments alone: on no launch geometry, not on the kernel variant (a block stages its source patch
+ * in LDS, or reads it from global memory where the patch of the largest listed scale exceeds 64 KB) and not on the
+ * alignment path; two calls give the same bytes.
+ * SVAE_EBADARG (checked on the host before any launch): null images or spec; target and target_u8 both null;
+ * target_u8 with fp32 images; nimg, H, W, c, h, w or n <= 0; n_scales outside 1 .. 4; a scale outside 1 .. 8 or
+ * listed twice; s*h > H or s*w > W for a listed scale; symmetries not in {1, 2, 4, 8}; 8 with h != w; lo >= hi
+ * with uint8 images.  SVAE_EBADCONFIG: H*W*c or h*w*c > 2^31 - 1. */
+typedef struct svae_crop_spec {
+  int32_t n_scales; int32_t scales[4];   /* integer box factors, each in 1..8, all distinct */
+  int32_t symmetries;                    /* 1: none, 2: mirror x, 4: mirror x and/or y, 8: dihedral group (needs h == w) */
+} svae_crop_spec;
+int svae_op_crop_batch(const void* images, int data_u8, int nimg, int H, int W, int c, int h, int w,
+                       const svae_crop_spec* spec, const int32_t* crops, uint64_t seed, uint64_t offset, int n,
+                       float lo, float hi, float* target, uint8_t* target_u8, int32_t* meta, void* stream);
 
 /* Overlapping tiles: the work around the forward when a network of tile size th x tw restores whole images (no
  * reference counterpart).  Both ops are one launch on `stream`, no allocation, no synchronisation, no atomics: the

@@ -51,6 +51,11 @@ class SvaeDegradeSpec(ctypes.Structure):
                 ("pepper_prob", ctypes.c_float), ("salt_prob", ctypes.c_float), ("gaussian_scale", ctypes.c_float)]
 
 
+class SvaeCropSpec(ctypes.Structure):
+    """svae_crop_spec (include/svae_hip.h)."""
+    _fields_ = [("n_scales", ctypes.c_int32), ("scales", ctypes.c_int32 * 4), ("symmetries", ctypes.c_int32)]
+
+
 class SvaeParamDesc(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 96), ("ndim", ctypes.c_int32), ("shape", ctypes.c_int32 * 4),
                 ("offset", ctypes.c_int64), ("init", ctypes.c_int32), ("flags", ctypes.c_int32)]
@@ -152,6 +157,8 @@ def _load(path):
         "svae_op_make_batch": ([vp, i32, vp, i64, i32, i64, f32, f32, f32, f32, f32, u64, u64, vp, vp, vp], i32),
         "svae_op_degrade_batch": ([vp, i32, i32, i32, i32, f32, f32, ctypes.POINTER(SvaeDegradeSpec), u64, u64, vp, vp,
                                    vp], i32),
+        "svae_op_crop_batch": ([vp, i32, i32, i32, i32, i32, i32, i32, ctypes.POINTER(SvaeCropSpec), vp, u64, u64, i32,
+                                f32, f32, vp, vp, vp, vp], i32),
         "svae_op_extract_tiles": ([vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, f32, i64, i64, vp, vp], i32),
         "svae_op_blend_tiles": ([vp, i32, i64, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, f32, f32, vp, vp,
                                  vp], i32),
@@ -180,6 +187,7 @@ def _load(path):
         "svae_set_backward_hook": ([vp, STEP_HOOK, vp], i32),
         "svae_hook_stream": ([vp], vp),
         "svae_set_chain_noise": ([vp, vp], i32),
+        "svae_rng_offset": ([vp, ctypes.POINTER(u64), ctypes.POINTER(u64)], i32),
         "svae_set_external_grads": ([vp, vp, vp], i32),
         "svae_bind_imp": ([vp, vp], i32),
         "svae_backward_imp": ([vp, vp], i32),
@@ -252,7 +260,8 @@ EXPORTED = ["svae_param_count", "svae_param_layout", "svae_create", "svae_destro
             "svae_op_splitfc_bwd", "svae_op_stats_plan", "svae_op_tensor_stats", "svae_op_wgrad_last_kernel",
             "svae_op_dense_bf16", "svae_op_fc_wgrad", "svae_op_image_metrics",
             "svae_op_mixture_logdensity", "svae_op_pairwise_scratch_bytes", "svae_op_pairwise_stats",
-            "svae_op_degrade_batch", "svae_op_extract_tiles", "svae_op_blend_tiles"]
+            "svae_op_degrade_batch", "svae_op_extract_tiles", "svae_op_blend_tiles", "svae_op_crop_batch",
+            "svae_rng_offset"]
 # include/svae_pcnn.h (the PixelCNN++ head)
 PCNN_EXPORTED = ["svae_pcnn_wnorm", "svae_pcnn_wnorm_bwd", "svae_pcnn_conv", "svae_pcnn_conv_wgrad", "svae_pcnn_colsum",
                  "svae_pcnn_colsum_absmax", "svae_pcnn_im2col_h16", "svae_pcnn_conv_planes_amax",

@@ -3150,6 +3150,13 @@ int svae_backward(svae_ctx* c, void* stream) {
   return 0;
 }
 
+int svae_rng_offset(svae_ctx* c, const uint64_t* set, uint64_t* get) {
+  if (!c) return fail(c, SVAE_EBADARG, "null ctx");
+  if (get) *get = c->rng_offset;
+  if (set) c->rng_offset = *set;
+  return 0;
+}
+
 int svae_set_chain_noise(svae_ctx* c, const float* noise) {
   if (!c) return fail(c, SVAE_EBADARG, "null ctx");
   if (noise && !c->m.g.noisy) return fail(c, SVAE_EBADARG, "add_noise_to_chain is off");
@@ -3813,6 +3820,45 @@ int svae_op_degrade_batch(const float* target, int n, int h, int w, int c, float
   a.nz.thr_pepper = prob_threshold(p.pepper_prob); a.nz.thr_salt = prob_threshold(p.salt_prob);
   a.nz.seed = seed; a.nz.offset = offset;
   degrade_batch(a, (hipStream_t)stream);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
+}
+
+int svae_op_crop_batch(const void* images, int data_u8, int nimg, int H, int W, int c, int h, int w,
+                       const svae_crop_spec* spec, const int32_t* crops, uint64_t seed, uint64_t offset, int n,
+                       float lo, float hi, float* target, uint8_t* target_u8, int32_t* meta, void* stream) {
+  if (!images || !spec) return fail(nullptr, SVAE_EBADARG, "crop_batch: null images or spec");
+  if (!target && !target_u8) return fail(nullptr, SVAE_EBADARG, "crop_batch: target and target_u8 are both null");
+  if (target_u8 && !data_u8) return fail(nullptr, SVAE_EBADARG, "crop_batch: target_u8 needs uint8 images");
+  if (nimg <= 0 || H <= 0 || W <= 0 || c <= 0 || h <= 0 || w <= 0 || n <= 0)
+    return fail(nullptr, SVAE_EBADARG, "crop_batch: nimg, H, W, c, h, w and n must be positive");
+  const svae_crop_spec& p = *spec;
+  if (p.n_scales < 1 || p.n_scales > 4) return fail(nullptr, SVAE_EBADARG, "crop_batch: n_scales must be in 1 .. 4");
+  int smax = 0;
+  for (int k = 0; k < p.n_scales; ++k) {
+    const int s = p.scales[k];
+    if (s < 1 || s > 8) return fail(nullptr, SVAE_EBADARG, "crop_batch: a scale outside 1 .. 8");
+    for (int j = 0; j < k; ++j)
+      if (p.scales[j] == s) return fail(nullptr, SVAE_EBADARG, "crop_batch: a scale is listed twice");
+    if ((int64_t)s * h > H || (int64_t)s * w > W)
+      return fail(nullptr, SVAE_EBADARG, "crop_batch: a scaled tile exceeds the image");
+    smax = std::max(smax, s);
+  }
+  if (p.symmetries != 1 && p.symmetries != 2 && p.symmetries != 4 && p.symmetries != 8)
+    return fail(nullptr, SVAE_EBADARG, "crop_batch: symmetries must be 1, 2, 4 or 8");
+  if (p.symmetries == 8 && h != w) return fail(nullptr, SVAE_EBADARG, "crop_batch: the dihedral group needs h == w");
+  if (data_u8 && !(lo < hi)) return fail(nullptr, SVAE_EBADARG, "crop_batch: lo >= hi with uint8 images");
+  if ((int64_t)H * W * c > 2147483647LL || (int64_t)h * w * c > 2147483647LL)
+    return fail(nullptr, SVAE_EBADCONFIG, "crop_batch: at most 2^31 - 1 elements per image and per tile");
+  CropArgs a{};
+  a.images = images; a.data_u8 = data_u8 ? 1 : 0;
+  a.nimg = nimg; a.H = H; a.W = W; a.c = c; a.h = h; a.w = w;
+  a.n_scales = p.n_scales; a.smax = smax; a.symmetries = p.symmetries;
+  for (int k = 0; k < 4; ++k) a.scales[k] = k < p.n_scales ? p.scales[k] : p.scales[0];
+  a.crops = crops; a.seed = seed; a.offset = offset; a.n = n;
+  a.lo = lo; a.qscale = (float)(((double)hi - (double)lo) / 255.0);
+  a.target = target; a.target_u8 = target_u8; a.meta = meta;
+  crop_batch(a, (hipStream_t)stream);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
 }

@@ -389,6 +389,21 @@ struct BlendTilesArgs {
 };
 void extract_tiles(const ExtractTilesArgs& a, hipStream_t s);
 void blend_tiles(const BlendTilesArgs& a, hipStream_t s);
+// ---- random crops (crops.hip): svae_op_crop_batch ----
+// row b of the batch = the h x w window at (y0, x0) of image m, box-averaged by s and mapped by symmetry g, with
+// (m, s, g, y0, x0) = crops[b], or drawn from Philox counter (offset + b, c2 = 4, c3 = block) when crops == nullptr
+struct CropArgs {
+  const void* images; int data_u8;
+  int nimg, H, W, c, h, w;
+  int n_scales, scales[4], smax;     // smax: the largest listed scale (what the LDS patch is sized for)
+  int symmetries;
+  const int* crops;
+  unsigned long long seed, offset;
+  int n;
+  float lo, qscale;                  // qscale = (hi - lo) / 255 rounded to fp32 (make_batch's)
+  float* target; unsigned char* target_u8; int* meta;   // target or target_u8 may be nullptr, meta may be
+};
+void crop_batch(const CropArgs& a, hipStream_t s);
 // ---- segmented statistics (stats.hip): the eight fp64 columns of svae_op_tensor_stats per segment ----
 // plan table (int64 words): [0, n_seg] the index of every segment's first chunk (entry n_seg = n_chunks), then
 // per chunk (begin, segment << 32 | length).  stats_plan returns the chunk count (table == nullptr: count only),

@@ -5,6 +5,8 @@ float32 cache and hand numpy batches to the trainer.  Here the images stay where
 them: uint8 (CelebA at 64x64x3 is 2.4 GB) or fp32 [N, H, W, C] tensors on the device, and a batch is a
 (start, B) window that svae_op_make_batch gathers, dequantises and corrupts in one launch
 (trainer.NoisyTrainer).  File decoders are out of scope: from_array takes what a decoder produced.
+
+PatchDataset holds images larger than the network's and serves random crops of them (svae_op_crop_batch).
 """
 import math
 
@@ -97,3 +99,70 @@ class DeviceDataset:
 
     def load_state_dict(self, s):
         self.train_idx, self.test_idx = int(s["train_idx"]), int(s["test_idx"])
+
+
+class PatchDataset(DeviceDataset):
+    """Large images on the device, seen through a network of tile size ``tile`` = (h, w): every training batch is a
+    set of fresh random crops (window, integer box scale, mirror / rotation: crops.CropSpec) made by one
+    svae_op_crop_batch launch (csrc/crops.hip), so neither a cut copy of the images nor a fixed tiling exists.
+
+    ``train_images`` / ``test_images`` are uint8 or float32 [N, H, W, C] device tensors of one dtype and channel
+    count (their extents may differ).  ``data_dims`` is the tile's [h, w, C].  ``.train`` and ``.test`` are fixed
+    sets of ``eval_crops`` crops each, made once here by the same op under ``eval_seed`` (rows 0 .. eval_crops - 1
+    of that key from the training images, the next eval_crops rows from the test images), uint8 for uint8 images
+    (the rounded block mean) and float32 otherwise: the cursor, test(), evaluate(), latent_information(),
+    sample_quality() and visualize walk them as they walk any DeviceDataset.  ``patch_batch`` is the training
+    batch; NoisyTrainer calls it instead of gathering rows of ``.train``."""
+
+    def __init__(self, train_images, test_images, tile, scales=(1,), symmetries=1, eval_crops=256, eval_seed=0,
+                 range=(-1.0, 1.0), name="patches"):
+        from . import crops
+        for t in (train_images, test_images):
+            if t.dim() != 4 or t.dtype not in (torch.uint8, torch.float32) or not t.is_cuda:
+                raise ValueError("PatchDataset holds uint8 or float32 [N, H, W, C] device tensors")
+        if train_images.dtype != test_images.dtype or train_images.shape[3] != test_images.shape[3]:
+            raise ValueError("train and test images must agree in dtype and channels")
+        h, w = int(tile[0]), int(tile[1])
+        self.spec = crops.CropSpec(tuple(scales), symmetries)
+        if self.spec.symmetries == 8 and h != w:
+            raise ValueError("the dihedral group needs a square tile, got %d x %d" % (h, w))
+        smax = max(self.spec.scales)
+        for t in (train_images, test_images):
+            if smax * h > t.shape[1] or smax * w > t.shape[2]:
+                raise ValueError("a %d x %d tile at scale %d exceeds the %d x %d images"
+                                 % (h, w, smax, t.shape[1], t.shape[2]))
+        if int(eval_crops) <= 0:
+            raise ValueError("eval_crops must be positive")
+        self.tile = (h, w)
+        self.train_images, self.test_images = train_images.contiguous(), test_images.contiguous()
+        self.eval_crops, self.eval_seed = int(eval_crops), int(eval_seed) & 0xFFFFFFFFFFFFFFFF
+        u8 = train_images.dtype == torch.uint8
+        fixed = []
+        for k, images in enumerate((self.train_images, self.test_images)):
+            out = torch.empty([self.eval_crops, h, w, int(images.shape[3])], dtype=images.dtype, device=images.device)
+            crops.crop_batch(images, self.tile, self.spec, self.eval_crops, self.eval_seed, k * self.eval_crops, range,
+                             out=None if u8 else out, out_u8=out if u8 else None)
+            fixed.append(out)
+        super().__init__(fixed[0], fixed[1], range=range, name=name)
+
+    @classmethod
+    def from_array(cls, arr, tile, test_fraction=0.2, range=(-1.0, 1.0), name="array", device=None, **kw):
+        """DeviceDataset.from_array's split of the large images: the first floor(N (1 - test_fraction)) train, the
+        rest test.  arr: uint8 or float [N, H, W, C] (numpy or torch); ``kw``: scales, symmetries, eval_crops,
+        eval_seed."""
+        t = arr if isinstance(arr, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(arr))
+        if t.dtype != torch.uint8:
+            t = t.to(torch.float32)
+        n_train = int(math.floor(t.shape[0] * (1.0 - test_fraction)))
+        if n_train <= 0 or n_train >= t.shape[0]:
+            raise ValueError("the split leaves an empty part")
+        if device is not None:
+            t = t.to(device)
+        return cls(t[:n_train], t[n_train:], tile, range=range, name=name, **kw)
+
+    def patch_batch(self, batch_size, seed, offset, out, meta=None):
+        """Fill the float32 [B, h, w, C] device tensor ``out`` with fresh crops of the training images: row b under
+        (seed, offset + b).  ``meta`` int32 [B, 5], when given, receives (m, s, g, y0, x0) per row."""
+        from . import crops
+        return crops.crop_batch(self.train_images, self.tile, self.spec, batch_size, seed, offset, self.range, out=out,
+                                meta=meta)

@@ -355,8 +355,11 @@ class SequentialVAE:
         # so after N updates it holds beta^(N+1) (tf.train.AdamOptimizer._create_slots / _finish)
         out["beta1_power"] = torch.tensor(0.9 ** (self.adam_updates + 1), dtype=torch.float32)
         out["beta2_power"] = torch.tensor(0.999 ** (self.adam_updates + 1), dtype=torch.float32)
+        rng = ctypes.c_uint64()
+        _lib.check(self.L.svae_rng_offset(self.ctx, None, ctypes.byref(rng)), self.ctx)
         save_file(out, path, metadata={"iteration": str(self.iteration), "learning_rate": repr(self.learning_rate),
-                                       "adam_updates": str(self.adam_updates), "config": self.name})
+                                       "adam_updates": str(self.adam_updates), "config": self.name,
+                                       "rng_offset": str(rng.value)})
 
     def load_checkpoint(self, path):
         """Restore save_checkpoint's state (init_network's restore, abstract_network.py:139-152);
@@ -396,6 +399,9 @@ class SequentialVAE:
             self.iteration = 0
             self.adam_updates = 0
         self.learning_rate = float(meta.get("learning_rate", self.learning_rate))
+        if "rng_offset" in meta:  # the engine's own draws (eps with none given) go on where the saved run stood
+            rng = ctypes.c_uint64(int(meta["rng_offset"]))
+            _lib.check(self.L.svae_rng_offset(self.ctx, ctypes.byref(rng), None), self.ctx)
 
     def generate(self, z=None, stream=None, noise=None):
         """Generator chain on latents z [T,B,Dz] (None: N(0,1) on device), no recognition network

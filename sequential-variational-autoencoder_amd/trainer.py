@@ -14,6 +14,11 @@ With ``degradation`` (a degrade.Degradation) the input is instead the clean targ
 out per image by svae_op_degrade_batch (csrc/degrade.hip), a second enqueue after a target-only make_batch, under
 the same seeds and offsets (its per-image draws come from a Philox stream make_batch leaves unused), followed by
 the pixel noise above when denoise_train is on.  No new state: state_dict() is what it was.
+
+With a data.PatchDataset the clean training target is instead a batch of fresh random crops of large images
+(svae_op_crop_batch, csrc/crops.hip) under the training seed and offset, and the input is derived from it as above;
+test batches and every evaluation walk the dataset's fixed sets of crops as they walk any dataset.  No new state
+either: train_offset, which is checkpointed, then advances every step.
 """
 import json
 import logging
@@ -136,6 +141,8 @@ class NoisyTrainer:
         """The next window as (input, target) device tensors; advances the cursor and, when it corrupts,
         the stream's offset."""
         ds = self.dataset
+        if not test and hasattr(ds, "patch_batch"):
+            return self._next_patches()
         start, _ = ds.next_test_batch(self.batch_size) if test else ds.next_batch(self.batch_size)
         data = ds.test if test else ds.train
         if test:
@@ -144,6 +151,30 @@ class NoisyTrainer:
         else:
             inp, corrupted = self._corrupted_batch(data, start, self.seed, self.train_offset)
             self.train_offset += self._groups() if corrupted else 0
+        return inp, self._target
+
+    def _next_patches(self):
+        """The training batch of a data.PatchDataset: self._target is ``batch_size`` fresh crops of the large
+        training images (one svae_op_crop_batch launch under (seed, train_offset + b): Philox stream 4, which neither
+        the pixel noise nor the degradation draws from, so the three share the key and the offset), and the input is
+        derived from that target as from any other: svae_op_make_batch on the fp32 target under denoise_train alone,
+        svae_op_degrade_batch under a degradation, the target itself otherwise.  train_offset advances by one batch
+        in every case (an uncorrupted run would otherwise redraw the same crops); the dataset's train cursor does
+        not move."""
+        ds = self.dataset
+        ds.patch_batch(self.batch_size, self.seed, self.train_offset, self._target)
+        inp = self._target
+        if self.degradation is not None:
+            from . import degrade
+            lo, hi = ds.range
+            noise = (self.pepper_prob, self.salt_prob, self.gaussian_noise_scale) if self.denoise_train \
+                else (0.0, 0.0, 0.0)
+            inp = degrade.degrade_batch(self._target, self.degradation, lo, hi, noise, self.seed, self.train_offset,
+                                        out=self._input)
+        elif self.denoise_train:
+            self._make_batch(self._target, 0, None, self._input, self.seed, self.train_offset)
+            inp = self._input
+        self.train_offset += self._groups()
         return inp, self._target
 
     # ------------------------------------------------------------------ the reference's loop

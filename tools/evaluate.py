@@ -4,7 +4,7 @@
     python tools/evaluate.py --netname celeba --version 1 --data faces.npy --denoise_train
     python tools/evaluate.py --netname tiny --synthetic 64 --batch_size 4 --denoise_train
 
-Give the data, --batch_size, --dtype and --denoise_train the run was trained with: the evaluation then scores the
+Give the data, --batch_size, --dtype, --denoise_train and the --patches flags the run was trained with: the evaluation then scores the
 validation set the run's own --eval_frequency lines scored, and reproduces the last of them when the checkpoint is
 that iteration's.  The seeds come from the run's trainer.json (--synthetic images and, unless --seed is given, the
 evaluation's draws).  Prints the result as one JSON line and writes it to eval.json next to the checkpoint.
@@ -44,6 +44,7 @@ def parse(argv=None):
                          "split's whole windows; written to sample_quality.json")
     ap.add_argument("--dtype", default="bf16x6", choices=["fp32", "bf16", "bf16x6"])
     importlib.import_module(PKG + ".degrade").add_flags(ap)
+    importlib.import_module(PKG + ".crops").add_flags(ap)
     ap.add_argument("--models_dir", default="models")
     return ap.parse_args(argv)
 
@@ -53,6 +54,35 @@ def degradation(a):
     return importlib.import_module(PKG + ".degrade").Degradation.from_flags(a.blur, a.downsample, a.cutout)
 
 
+def patch_options(a):
+    """PatchDataset's keywords from --patches, --patch_scales, --patch_symmetries and --eval_crops (None: no --patches)."""
+    if not a.patches:
+        return None
+    spec = importlib.import_module(PKG + ".crops").CropSpec.from_flags(a.patch_scales, a.patch_symmetries)
+    return dict(scales=spec.scales, symmetries=spec.symmetries, eval_crops=a.eval_crops)
+
+
+def dataset(a, cfg, seed):
+    """The DeviceDataset of --data / --synthetic; with --patches a PatchDataset over large images (--synthetic then
+    makes images of four tiles a side), its fixed evaluation crops drawn under ``seed``."""
+    import numpy as np
+    data = importlib.import_module(PKG + ".data")
+    po = patch_options(a)
+    if po is None:
+        if a.data:
+            return data.DeviceDataset.from_array(np.load(a.data), range=cfg.range, name=os.path.basename(a.data),
+                                                 device="cuda")
+        return data.DeviceDataset.synthetic(a.synthetic, cfg.height, cfg.width, cfg.channels, seed=seed,
+                                            range=cfg.range, device="cuda")
+    tile = (cfg.height, cfg.width)
+    if a.data:
+        return data.PatchDataset.from_array(np.load(a.data), tile, range=cfg.range, name=os.path.basename(a.data),
+                                            device="cuda", eval_seed=seed, **po)
+    big = data.DeviceDataset.synthetic(a.synthetic, 4 * cfg.height, 4 * cfg.width, cfg.channels, seed=seed,
+                                       range=cfg.range, device="cuda")
+    return data.PatchDataset(big.train, big.test, tile, range=cfg.range, name="synthetic", eval_seed=seed, **po)
+
+
 def main(argv=None):
     a = parse(argv)
     base_dir = os.path.join(a.models_dir, "%s_v%d" % (a.netname, a.version))
@@ -60,14 +90,12 @@ def main(argv=None):
     if not os.path.exists(ckpt):
         print("no checkpoint at %s" % ckpt)
         return 1
-    import numpy as np
     import torch
     if not torch.cuda.is_available():
         print("tools/evaluate.py needs a GPU (the engine has no CPU path)")
         return 1
     cfgmod = importlib.import_module(PKG + ".config")
     SV = importlib.import_module(PKG + ".sequential_vae").SequentialVAE
-    DS = importlib.import_module(PKG + ".data").DeviceDataset
     NT = importlib.import_module(PKG + ".trainer").NoisyTrainer
     over = dict(dtype=a.dtype)
     if a.batch_size:
@@ -78,11 +106,7 @@ def main(argv=None):
         with open(os.path.join(base_dir, "trainer.json")) as f:
             state = json.load(f)
     run_seed = int(state.get("seed", 0))
-    if a.data:
-        ds = DS.from_array(np.load(a.data), range=cfg.range, name=os.path.basename(a.data), device="cuda")
-    else:
-        ds = DS.synthetic(a.synthetic, cfg.height, cfg.width, cfg.channels, seed=run_seed, range=cfg.range,
-                          device="cuda")
+    ds = dataset(a, cfg, run_seed)
     net = SV(cfg, seed=run_seed)
     net.name = a.netname
     net.load_checkpoint(ckpt)

@@ -2,10 +2,13 @@
 
     python tools/train.py --netname celeba --data faces.npy --denoise_train --plot_reconstruction
     python tools/train.py --netname tiny --synthetic 64 --batch_size 4 --iters 100
+    python tools/train.py --netname celeba --data photos.npy --patches --patch_scales 1,2 --patch_symmetries 8
 
 --data is an .npy file of uint8 or float images [N, H, W, C] (what a decoder of CelebA / LSUN / SVHN
 produced; the decoders themselves are not part of this project); --synthetic N makes N seeded images of
-the preset's shape.  The model directory is models/<netname>_v<version>: an existing one is refused
+the preset's shape.  With --patches the images are larger than the preset's (any size that holds a tile at the
+largest scale): every training batch is fresh random crops of them (data.PatchDataset) and the test and evaluation
+sets are --eval_crops fixed crops.  The model directory is models/<netname>_v<version>: an existing one is refused
 without --continue_training, a missing one with it, as main.py:52-58 does.
 """
 import argparse
@@ -48,6 +51,7 @@ def parse(argv=None):
     ap.add_argument("--iters", type=int, default=None, help="iterations to run (default: the reference's 10^7)")
     ap.add_argument("--dtype", default="bf16x6", choices=["fp32", "bf16", "bf16x6"])
     importlib.import_module(PKG + ".degrade").add_flags(ap)
+    importlib.import_module(PKG + ".crops").add_flags(ap)
     ap.add_argument("--models_dir", default="models")
     ap.add_argument("--seed", type=int, default=0)
     return ap.parse_args(argv)
@@ -67,6 +71,35 @@ def degradation(a):
     return importlib.import_module(PKG + ".degrade").Degradation.from_flags(a.blur, a.downsample, a.cutout)
 
 
+def patch_options(a):
+    """PatchDataset's keywords from --patches, --patch_scales, --patch_symmetries and --eval_crops (None: no --patches)."""
+    if not a.patches:
+        return None
+    spec = importlib.import_module(PKG + ".crops").CropSpec.from_flags(a.patch_scales, a.patch_symmetries)
+    return dict(scales=spec.scales, symmetries=spec.symmetries, eval_crops=a.eval_crops)
+
+
+def dataset(a, cfg, seed):
+    """The DeviceDataset of --data / --synthetic; with --patches a PatchDataset over large images (--synthetic then
+    makes images of four tiles a side), its fixed evaluation crops drawn under ``seed``."""
+    import numpy as np
+    data = importlib.import_module(PKG + ".data")
+    po = patch_options(a)
+    if po is None:
+        if a.data:
+            return data.DeviceDataset.from_array(np.load(a.data), range=cfg.range, name=os.path.basename(a.data),
+                                                 device="cuda")
+        return data.DeviceDataset.synthetic(a.synthetic, cfg.height, cfg.width, cfg.channels, seed=seed,
+                                            range=cfg.range, device="cuda")
+    tile = (cfg.height, cfg.width)
+    if a.data:
+        return data.PatchDataset.from_array(np.load(a.data), tile, range=cfg.range, name=os.path.basename(a.data),
+                                            device="cuda", eval_seed=seed, **po)
+    big = data.DeviceDataset.synthetic(a.synthetic, 4 * cfg.height, 4 * cfg.width, cfg.channels, seed=seed,
+                                       range=cfg.range, device="cuda")
+    return data.PatchDataset(big.train, big.test, tile, range=cfg.range, name="synthetic", eval_seed=seed, **po)
+
+
 def main(argv=None):
     a = parse(argv)
     base_dir = os.path.join(a.models_dir, "%s_v%d" % (a.netname, a.version))
@@ -74,23 +107,18 @@ def main(argv=None):
     if err:
         print(err)
         return 1
-    import numpy as np
     import torch
     if not torch.cuda.is_available():
         print("tools/train.py needs a GPU (the engine has no CPU path)")
         return 1
     cfgmod = importlib.import_module(PKG + ".config")
     SV = importlib.import_module(PKG + ".sequential_vae").SequentialVAE
-    DS = importlib.import_module(PKG + ".data").DeviceDataset
     NT = importlib.import_module(PKG + ".trainer").NoisyTrainer
     over = dict(dtype=a.dtype)
     if a.batch_size:
         over["batch"] = a.batch_size
     cfg = cfgmod.preset(a.netname, **over)
-    if a.data:
-        ds = DS.from_array(np.load(a.data), range=cfg.range, name=os.path.basename(a.data), device="cuda")
-    else:
-        ds = DS.synthetic(a.synthetic, cfg.height, cfg.width, cfg.channels, seed=a.seed, range=cfg.range, device="cuda")
+    ds = dataset(a, cfg, a.seed)
     os.makedirs(base_dir, exist_ok=True)
     logging.basicConfig(filename=os.path.join(base_dir, "log"), level=logging.INFO)
     log = logging.getLogger(a.netname)
