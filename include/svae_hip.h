@@ -462,6 +462,59 @@ int svae_op_crop_batch(const void* images, int data_u8, int nimg, int H, int W, 
                        const svae_crop_spec* spec, const int32_t* crops, uint64_t seed, uint64_t offset, int n,
                        float lo, float hi, float* target, uint8_t* target_u8, int32_t* meta, void* stream);
 
+/* JPEG compression artefacts on a batch in one launch on `stream` (no allocation, no synchronisation, no atomics; no
+ * reference counterpart: the inputs of deblocking and de-ringing runs).  in and out are [n,h,w,c] fp32 with values in
+ * [lo, hi], c = 1 (grey) or 3 (RGB); out == in is legal (any other overlap is the caller's contract).  quality [n]
+ * int32 (may be NULL) receives the quality used, 0 for an image that was not compressed.  There is no entropy
+ * coding: only the decoded pixels exist.
+ * Draws per image b: Philox4x32-10 under the key (lo32(seed), hi32(seed)) with the 64-bit value offset + b in the
+ * counter words (c0, c1), c2 = 5 (a stream neither svae_op_make_batch, 0 .. 2, svae_op_degrade_batch, 3, nor
+ * svae_op_crop_batch, 4, uses) and c3 = 0.  With the words a0..a3: compress iff a0 < thr(p), q = q_lo +
+ * mulhi(a1, q_hi - q_lo + 1), thr and mulhi as above.  An image that is not compressed is copied byte for byte (in
+ * place: nothing is done).  A compressed image, in this order, every product, sum and division rounded to fp32 on its
+ * own, sums left to right as written:
+ *   1 levels    L = clamp(rintf((x - lo) * (255 / (hi - lo))), 0, 255), the constant rounded to fp32 (rintf: ties to even)
+ *   2 colour    (c = 3) JFIF full-range BT.601 with fp32 constants:
+ *                 Y  = 0.299 R + 0.587 G + 0.114 B
+ *                 Cb = 128 - 0.168735892 R - 0.331264108 G + 0.5 B
+ *                 Cr = 128 + 0.5 R - 0.418687589 G - 0.081312411 B
+ *               each then rintf and clamped to [0, 255], as a codec's 8-bit component planes are.  c = 1: Y = L.
+ *   3 chroma    subsample = 1 (4:4:4): the chroma planes are h x w.  subsample = 2 (4:2:0; c = 3 only, ignored for
+ *               c = 1): they are ceil(h/2) x ceil(w/2), each value the mean of the in-image pixels of its 2 x 2 block:
+ *               sequential fp32 adds from 0 in row-major order, then one correctly rounded fp32 division by the count.
+ *               The means are not rounded to integers.
+ *   4 blocks    each plane is extended to multiples of 8 by replicating its last row and column; 128 is subtracted
+ *               from every value.  Per 8 x 8 block f, F = C f C^T with C[u][x] = cos((2x + 1) u pi / 16) / 2 and
+ *               C[0][x] = 1 / sqrt(8), a table of the fp32 constants 0.353553391 (u = 0), then for m = (2x + 1) u
+ *               folded into the first octant (cos(m pi / 16) / 2, m = 1 .. 7, with its sign): 0.490392640,
+ *               0.461939766, 0.415734806, 0.353553391, 0.277785117, 0.191341716, 0.0975451610.  Row pass first:
+ *               t[y][u] = sum_x f[y][x] * C[u][x] from 0 in ascending x; then the column pass F[v][u] =
+ *               sum_y C[v][y] * t[y][u] from 0 in ascending y.
+ *   5 quantiser the JPEG standard's Annex K luminance (Y) and chrominance (Cb, Cr) tables in natural order, IJG
+ *               scaling in integers: s = q < 50 ? 5000 / q : 200 - 2 q, T = clamp((base * s + 50) / 100, 1, 255).
+ *               k = rintf(F / (float)T), the division correctly rounded; dequantised G = k * T.
+ *   6 inverse   column pass s[y][u] = sum_v C[v][y] * G[v][u], then row pass g[y][x] = sum_u s[y][u] * C[u][x], both
+ *               from 0 in ascending order; then rintf(g + 128) clamped to [0, 255].
+ *   7 chroma up subsample = 2: pixel (i, j) reads chroma (i / 2, j / 2).
+ *   8 colour    (c = 3)  R = Y + 1.402 (Cr - 128),  G = Y - 0.344136286 (Cb - 128) - 0.714136286 (Cr - 128),
+ *               B = Y + 1.772 (Cb - 128); then rintf, clamped to [0, 255].  c = 1: L' = Y.
+ *   9 out       lo + L' * ((hi - lo) / 255) with the constant, the product and the sum each rounded to fp32, word for
+ *               word svae_op_make_batch's dequantisation.
+ * The result depends on the arguments alone: on no launch geometry and not on the alignment path (16-byte accesses
+ * where the base and h*w*c rows allow, element by element otherwise); two calls give the same bytes.  A block of
+ * threads owns 16 x 16 pixels, so no image size exceeds what a block can hold.
+ * SVAE_EBADARG (checked on the host before any launch): null in, out or spec; n, h or w <= 0; c not in {1, 3}; p
+ * outside [0, 1]; q_lo < 1, q_hi > 100 or q_lo > q_hi; subsample not in {1, 2}; lo >= hi.  SVAE_EBADCONFIG:
+ * h*w*c > 2^31 - 1. */
+typedef struct svae_jpeg_spec {
+  float p;                 /* probability per image */
+  int32_t q_lo, q_hi;      /* IJG quality, uniform integer in [q_lo, q_hi], 1 <= q_lo <= q_hi <= 100 */
+  int32_t subsample;       /* 1: 4:4:4, 2: 4:2:0 (c == 3 only; ignored for c == 1) */
+} svae_jpeg_spec;
+int svae_op_jpeg_batch(const float* in, int n, int h, int w, int c, float lo, float hi,
+                       const svae_jpeg_spec* spec, uint64_t seed, uint64_t offset,
+                       float* out, int32_t* quality, void* stream);
+
 /* Overlapping tiles: the work around the forward when a network of tile size th x tw restores whole images (no
  * reference counterpart).  Both ops are one launch on `stream`, no allocation, no synchronisation, no atomics: the
  * result depends on the arguments alone (on no launch geometry, not on the alignment path or the kernel variant),

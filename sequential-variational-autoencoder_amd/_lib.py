@@ -56,6 +56,12 @@ class SvaeCropSpec(ctypes.Structure):
     _fields_ = [("n_scales", ctypes.c_int32), ("scales", ctypes.c_int32 * 4), ("symmetries", ctypes.c_int32)]
 
 
+class SvaeJpegSpec(ctypes.Structure):
+    """svae_jpeg_spec (include/svae_hip.h)."""
+    _fields_ = [("p", ctypes.c_float), ("q_lo", ctypes.c_int32), ("q_hi", ctypes.c_int32),
+                ("subsample", ctypes.c_int32)]
+
+
 class SvaeParamDesc(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 96), ("ndim", ctypes.c_int32), ("shape", ctypes.c_int32 * 4),
                 ("offset", ctypes.c_int64), ("init", ctypes.c_int32), ("flags", ctypes.c_int32)]
@@ -159,6 +165,8 @@ def _load(path):
                                    vp], i32),
         "svae_op_crop_batch": ([vp, i32, i32, i32, i32, i32, i32, i32, ctypes.POINTER(SvaeCropSpec), vp, u64, u64, i32,
                                 f32, f32, vp, vp, vp, vp], i32),
+        "svae_op_jpeg_batch": ([vp, i32, i32, i32, i32, f32, f32, ctypes.POINTER(SvaeJpegSpec), u64, u64, vp, vp, vp],
+                               i32),
         "svae_op_extract_tiles": ([vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, f32, i64, i64, vp, vp], i32),
         "svae_op_blend_tiles": ([vp, i32, i64, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, f32, f32, vp, vp,
                                  vp], i32),
@@ -261,7 +269,7 @@ EXPORTED = ["svae_param_count", "svae_param_layout", "svae_create", "svae_destro
             "svae_op_dense_bf16", "svae_op_fc_wgrad", "svae_op_image_metrics",
             "svae_op_mixture_logdensity", "svae_op_pairwise_scratch_bytes", "svae_op_pairwise_stats",
             "svae_op_degrade_batch", "svae_op_extract_tiles", "svae_op_blend_tiles", "svae_op_crop_batch",
-            "svae_rng_offset"]
+            "svae_op_jpeg_batch", "svae_rng_offset"]
 # include/svae_pcnn.h (the PixelCNN++ head)
 PCNN_EXPORTED = ["svae_pcnn_wnorm", "svae_pcnn_wnorm_bwd", "svae_pcnn_conv", "svae_pcnn_conv_wgrad", "svae_pcnn_colsum",
                  "svae_pcnn_colsum_absmax", "svae_pcnn_im2col_h16", "svae_pcnn_conv_planes_amax",

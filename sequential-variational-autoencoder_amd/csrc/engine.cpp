@@ -3863,6 +3863,33 @@ int svae_op_crop_batch(const void* images, int data_u8, int nimg, int H, int W, 
   return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
 }
 
+int svae_op_jpeg_batch(const float* in, int n, int h, int w, int c, float lo, float hi, const svae_jpeg_spec* spec,
+                       uint64_t seed, uint64_t offset, float* out, int32_t* quality, void* stream) {
+  if (!in || !out || !spec) return fail(nullptr, SVAE_EBADARG, "jpeg_batch: null in, out or spec");
+  if (n <= 0 || h <= 0 || w <= 0) return fail(nullptr, SVAE_EBADARG, "jpeg_batch: n, h and w must be positive");
+  if (c != 1 && c != 3) return fail(nullptr, SVAE_EBADARG, "jpeg_batch: c must be 1 or 3");
+  const svae_jpeg_spec& p = *spec;
+  if (!(p.p >= 0.f && p.p <= 1.f)) return fail(nullptr, SVAE_EBADARG, "jpeg_batch: a probability outside [0, 1]");
+  if (p.q_lo < 1 || p.q_hi > 100 || p.q_lo > p.q_hi)
+    return fail(nullptr, SVAE_EBADARG, "jpeg_batch: need 1 <= q_lo <= q_hi <= 100");
+  if (p.subsample != 1 && p.subsample != 2) return fail(nullptr, SVAE_EBADARG, "jpeg_batch: subsample must be 1 or 2");
+  if (!(lo < hi)) return fail(nullptr, SVAE_EBADARG, "jpeg_batch: lo >= hi");
+  if ((int64_t)h * w * c > 2147483647LL)
+    return fail(nullptr, SVAE_EBADCONFIG, "jpeg_batch: at most 2^31 - 1 elements per image");
+  JpegArgs a{};
+  a.in = in; a.out = out; a.quality = quality;
+  a.n = n; a.h = h; a.w = w; a.c = c;
+  a.thr = prob_threshold(p.p);
+  a.q_lo = p.q_lo; a.q_hi = p.q_hi; a.subsample = c == 3 ? p.subsample : 1;
+  a.lo = lo;
+  a.qscale = (float)(((double)hi - (double)lo) / 255.0);
+  a.qinv = (float)(255.0 / ((double)hi - (double)lo));
+  a.seed = seed; a.offset = offset;
+  jpeg_batch(a, (hipStream_t)stream);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
+}
+
 // ---- overlapping tiles (tiles.hip) ----
 static int tile_count(int L, int t, int s) { return (int)(((int64_t)L - t + s - 1) / s) + 1; }
 

@@ -404,6 +404,18 @@ struct CropArgs {
   float* target; unsigned char* target_u8; int* meta;   // target or target_u8 may be nullptr, meta may be
 };
 void crop_batch(const CropArgs& a, hipStream_t s);
+// ---- JPEG artefacts (jpeg.hip): svae_op_jpeg_batch ----
+// in [n,h,w,c] -> out (may be in), quality [n] (may be nullptr), one launch.  Image b is compressed iff word a0 of
+// Philox counter (offset + b, c2 = 5, c3 = 0) is below thr, at quality q_lo + mulhi(a1, q_hi - q_lo + 1)
+struct JpegArgs {
+  const float* in; float* out; int* quality;
+  int n, h, w, c;
+  unsigned thr;
+  int q_lo, q_hi, subsample;         // subsample 2 only with c == 3 (the entry point makes it 1 for c == 1)
+  float lo, qscale, qinv;            // qscale = (hi - lo) / 255, qinv = 255 / (hi - lo), each rounded to fp32
+  unsigned long long seed, offset;
+};
+void jpeg_batch(const JpegArgs& a, hipStream_t s);
 // ---- segmented statistics (stats.hip): the eight fp64 columns of svae_op_tensor_stats per segment ----
 // plan table (int64 words): [0, n_seg] the index of every segment's first chunk (entry n_seg = n_chunks), then
 // per chunk (begin, segment << 32 | length).  stats_plan returns the chunk count (table == nullptr: count only),

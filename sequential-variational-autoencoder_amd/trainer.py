@@ -13,7 +13,9 @@ state_dict(), so a resumed run corrupts its next batch exactly as the uninterrup
 With ``degradation`` (a degrade.Degradation) the input is instead the clean target blurred, down-sampled and cut
 out per image by svae_op_degrade_batch (csrc/degrade.hip), a second enqueue after a target-only make_batch, under
 the same seeds and offsets (its per-image draws come from a Philox stream make_batch leaves unused), followed by
-the pixel noise above when denoise_train is on.  No new state: state_dict() is what it was.
+the pixel noise above when denoise_train is on.  A degradation whose ``jpeg`` stage has p > 0 then puts that input
+through svae_op_jpeg_batch (csrc/jpeg.hip) in place, a third enqueue under the same seed and offset (Philox stream
+5): sensor noise first, then compression.  No new state: state_dict() is what it was.
 
 With a data.PatchDataset the clean training target is instead a batch of fresh random crops of large images
 (svae_op_crop_batch, csrc/crops.hip) under the training seed and offset, and the input is derived from it as above;
@@ -110,19 +112,29 @@ class NoisyTrainer:
         no draw is made (corrupted is False: the caller leaves its offset alone).  With denoise_train alone it is
         svae_op_make_batch's noisy copy under (seed, offset).  With a degradation it is svae_op_degrade_batch of
         the clean target under the same (seed, offset), the pixel noise being the class constants under
-        denoise_train and zero otherwise.  A corrupting call consumes ceil(B H W C / 4) counters."""
+        denoise_train and zero otherwise, followed by svae_op_jpeg_batch in place where its jpeg stage has p > 0
+        (_degraded).  A corrupting call consumes ceil(B H W C / 4) counters."""
         if self.degradation is None:
             if not self.denoise_train:
                 self._make_batch(data, start, self._target, None, 0, 0, noise=False)
                 return self._target, False
             self._make_batch(data, start, self._target, self._input, seed, offset)
             return self._input, True
-        from . import degrade
         self._make_batch(data, start, self._target, None, 0, 0, noise=False)
+        return self._degraded(seed, offset), True
+
+    def _degraded(self, seed, offset):
+        """self._input as the degradation's copy of the clean self._target under (seed, offset):
+        svae_op_degrade_batch with the pixel noise of denoise_train, then, where the jpeg stage has p > 0,
+        svae_op_jpeg_batch in place on the result (image b under the counter offset + b of Philox stream 5, which no
+        other draw of the batch uses).  With jpeg at p = 0 nothing is launched for it."""
+        from . import degrade
         lo, hi = self.dataset.range
         noise = (self.pepper_prob, self.salt_prob, self.gaussian_noise_scale) if self.denoise_train else (0.0, 0.0, 0.0)
         degrade.degrade_batch(self._target, self.degradation, lo, hi, noise, seed, offset, out=self._input)
-        return self._input, True
+        if self.degradation.jpeg[0] > 0.0:
+            degrade.jpeg_batch(self._input, self.degradation, lo, hi, seed, offset)
+        return self._input
 
     def apply_noise(self, batch):
         """The reference's apply_noise on a given fp32 device batch [B,H,W,C], in place (the same kernel
@@ -158,19 +170,14 @@ class NoisyTrainer:
         training images (one svae_op_crop_batch launch under (seed, train_offset + b): Philox stream 4, which neither
         the pixel noise nor the degradation draws from, so the three share the key and the offset), and the input is
         derived from that target as from any other: svae_op_make_batch on the fp32 target under denoise_train alone,
-        svae_op_degrade_batch under a degradation, the target itself otherwise.  train_offset advances by one batch
-        in every case (an uncorrupted run would otherwise redraw the same crops); the dataset's train cursor does
+        svae_op_degrade_batch (and svae_op_jpeg_batch: _degraded) under a degradation, the target itself otherwise.
+        train_offset advances by one batch in every case (an uncorrupted run would otherwise redraw the same crops); the dataset's train cursor does
         not move."""
         ds = self.dataset
         ds.patch_batch(self.batch_size, self.seed, self.train_offset, self._target)
         inp = self._target
         if self.degradation is not None:
-            from . import degrade
-            lo, hi = ds.range
-            noise = (self.pepper_prob, self.salt_prob, self.gaussian_noise_scale) if self.denoise_train \
-                else (0.0, 0.0, 0.0)
-            inp = degrade.degrade_batch(self._target, self.degradation, lo, hi, noise, self.seed, self.train_offset,
-                                        out=self._input)
+            inp = self._degraded(self.seed, self.train_offset)
         elif self.denoise_train:
             self._make_batch(self._target, 0, None, self._input, self.seed, self.train_offset)
             inp = self._input

@@ -50,8 +50,8 @@ def parse(argv=None):
 
 
 def degradation(a):
-    """The Degradation --blur, --downsample and --cutout name (None: none of them given)."""
-    return importlib.import_module(PKG + ".degrade").Degradation.from_flags(a.blur, a.downsample, a.cutout)
+    """The Degradation --blur, --downsample, --cutout and --jpeg name (None: none of them given)."""
+    return importlib.import_module(PKG + ".degrade").Degradation.from_flags(a.blur, a.downsample, a.cutout, a.jpeg)
 
 
 def patch_options(a):

@@ -67,8 +67,8 @@ def model_dir_error(base_dir, continue_training):
 
 
 def degradation(a):
-    """The Degradation --blur, --downsample and --cutout name (None: none of them given)."""
-    return importlib.import_module(PKG + ".degrade").Degradation.from_flags(a.blur, a.downsample, a.cutout)
+    """The Degradation --blur, --downsample, --cutout and --jpeg name (None: none of them given)."""
+    return importlib.import_module(PKG + ".degrade").Degradation.from_flags(a.blur, a.downsample, a.cutout, a.jpeg)
 
 
 def patch_options(a):
