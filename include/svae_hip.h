@@ -682,6 +682,40 @@ int svae_op_pairwise_stats(const float* x, int64_t n, int64_t ldx, const float* 
                            const double* inv_two_sigma2, int n_bw, double* ksum, double* nn_d2, int64_t* nn_idx,
                            void* scratch, void* stream);
 
+/* Binned power spectra of a stack of images and of their differences to reference images, one launch on `stream`
+ * (no allocation, no synchronisation; no reference counterpart: the numbers behind NoisyTrainer.spectrum).
+ * x [n, h, w, c] and y [ny, h, w, c] or NULL are fp32 NHWC on the device at any alignment; image i of x is paired
+ * with image i % ny of y, as in svae_op_image_metrics.  The tables are the caller's, on the device: win_y [h] and
+ * win_x [w] (fp64), tw_y [h][2] and tw_x [w][2] with tw[k] = (cos 2 pi k / len, -sin 2 pi k / len) (fp64), and
+ * bin [h][wu], wu = w / 2 + 1 (int32): the output bin of spectrum entry (v, u), any value outside [0, n_bins)
+ * (-1 by convention) leaves the entry out.  out is [n][c][2][n_bins] fp64: plane 0 the binned power of the windowed
+ * image, plane 1 that of the windowed difference x - y (not touched when y == NULL); rows past n are not touched, a
+ * bin no entry maps to is written 0.  nonfinite [n][c] (int64, may be NULL) counts the NaN and +-inf among the
+ * elements read for that row: channel k of image i and, when y is given, of its partner.
+ * Per (image i, channel k, plane), everything after the load in fp64 on the vector ALU, every product, sum and
+ * difference rounded once in the order written (no fused multiply-add, no matrix instruction, no atomics):
+ *   a[yy][xx] = ((double)value * win_y[yy]) * win_x[xx]; in plane 1 the value is (double)x - (double)y, which is exact
+ *   T[yy][u]  = sum_xx a[yy][xx] * tw_x[(u xx) mod w]   for u in [0, w / 2], from 0 in ascending xx (a real times a
+ *               complex number: two products)
+ *   F[v][u]   = sum_yy T[yy][u] * tw_y[(v yy) mod h]    from 0 in ascending yy, the complex product as
+ *               (Tr c - Ti s, Tr s + Ti c) with tw = (c, s), each part added to its sum
+ *   P[v][u]   = (Re F * Re F + Im F * Im F) * m(u), m(u) = 1 for u = 0 and for u = w / 2 with w even, 2 otherwise
+ *   out[b]    = sum_u ( sum over the v with bin[v][u] == b of P[v][u], from 0 in ascending v ), from 0 in ascending u
+ *               (a column without such an entry adds 0)
+ * The op calls no trigonometric function; the table index is reduced in integers.  Row (i, k) depends on image i,
+ * its partner and the tables only: not on n, on the grid, on an address or on the load path (16-byte loads where
+ * the images are 16-byte aligned, element by element where not: the same values either way); two calls give the
+ * same bytes.  A non-finite element makes the rows that read it NaN or inf and no others.
+ * SVAE_EBADARG (checked on the host before any device call): a null pointer other than y and nonfinite; n, ny, c or
+ * n_bins <= 0 (ny also when y == NULL); h or w < 2; n not a multiple of ny when y is given.  SVAE_EBADCONFIG: h or
+ * w > SVAE_SPECTRUM_MAX_DIM (the plane and its half spectrum live in LDS), n_bins > SVAE_SPECTRUM_MAX_BINS,
+ * h * w * c or n * c > 2^31 - 1. */
+#define SVAE_SPECTRUM_MAX_DIM 96
+#define SVAE_SPECTRUM_MAX_BINS 64
+int svae_op_power_spectrum(const float* x, int n, const float* y, int ny, int h, int w, int c, const double* win_y,
+                           const double* win_x, const double* tw_y, const double* tw_x, const int32_t* bin, int n_bins,
+                           double* out, int64_t* nonfinite, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4100,4 +4100,24 @@ int svae_op_pairwise_stats(const float* x, int64_t n, int64_t ldx, const float* 
   return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
 }
 
+int svae_op_power_spectrum(const float* x, int n, const float* y, int ny, int h, int w, int c, const double* win_y,
+                           const double* win_x, const double* tw_y, const double* tw_x, const int32_t* bin, int n_bins,
+                           double* out, int64_t* nonfinite, void* stream) {
+  if (!x || !win_y || !win_x || !tw_y || !tw_x || !bin || !out)
+    return fail(nullptr, SVAE_EBADARG, "power_spectrum: null pointer");
+  if (n <= 0 || ny <= 0 || c <= 0 || n_bins <= 0)
+    return fail(nullptr, SVAE_EBADARG, "power_spectrum: n, ny, c and n_bins must be positive");
+  if (h < 2 || w < 2) return fail(nullptr, SVAE_EBADARG, "power_spectrum: h and w must be at least 2");
+  if (y && n % ny != 0) return fail(nullptr, SVAE_EBADARG, "power_spectrum: n must be a multiple of ny");
+  if (h > SVAE_SPECTRUM_MAX_DIM || w > SVAE_SPECTRUM_MAX_DIM || n_bins > SVAE_SPECTRUM_MAX_BINS)
+    return fail(nullptr, SVAE_EBADCONFIG, "power_spectrum: at most " + std::to_string(SVAE_SPECTRUM_MAX_DIM) +
+                                              " rows and columns and " + std::to_string(SVAE_SPECTRUM_MAX_BINS) +
+                                              " bins");
+  if ((int64_t)h * w * c > 2147483647LL || (int64_t)n * c > 2147483647LL)
+    return fail(nullptr, SVAE_EBADCONFIG, "power_spectrum: h * w * c or n * c above 2^31 - 1");
+  hipError_t e = power_spectrum(x, n, y, ny, h, w, c, win_y, win_x, tw_y, tw_x, bin, n_bins, out,
+                                (long long*)nonfinite, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
+}
+
 }  // extern "C"

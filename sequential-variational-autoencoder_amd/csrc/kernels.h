@@ -440,6 +440,12 @@ long long pairwise_scratch_bytes(long long n, const long long* m, int n_groups, 
 void pairwise_stats(const float* x, long long n, long long ldx, const float* const* y, const long long* m,
                     const long long* ldy, int n_groups, int d, int self_group, const double* inv_two_sigma2,
                     int n_bw, double* ksum, double* nn_d2, long long* nn_idx, void* scratch, hipStream_t s);
+// ---- binned power spectra (spectrum.hip): svae_op_power_spectrum's [n][c][2][n_bins] fp64 table, one launch on s ----
+// y == nullptr: plane 0 only; nonfinite [n][c] may be nullptr; arguments as checked by the entry point; returns the
+// error of the once-per-device dynamic-LDS attribute or of the launch
+hipError_t power_spectrum(const float* x, int n, const float* y, int ny, int h, int w, int c, const double* win_y,
+                          const double* win_x, const double* tw_y, const double* tw_x, const int* bin, int n_bins,
+                          double* out, long long* nonfinite, hipStream_t s);
 // column sums of X [rows][C<=4] -> out0[0..n0), out1[0..C-n0)   (part: scratch >= 1024 floats)
 void colsum_small(const float* X, int ld, long long rows, int C, float* part, float* out0, int n0, float* out1,
                   hipStream_t s);

@@ -48,7 +48,7 @@ class NoisyTrainer:
 
     def __init__(self, network, dataset, denoise_train=False, vis_frequency=1000, plot_reconstruction=False,
                  base_dir=None, logger=None, seed=0, summary_freq=0, eval_frequency=0, info_frequency=0,
-                 quality_frequency=0, degradation=None):
+                 quality_frequency=0, degradation=None, spectrum_frequency=0):
         if list(dataset.data_dims) != list(network.data_dims):
             raise ValueError("dataset images %s, network %s" % (dataset.data_dims, network.data_dims))
         if tuple(dataset.range) != tuple(float(v) for v in network.cfg.range):
@@ -78,7 +78,11 @@ class NoisyTrainer:
         # every quality_frequency-th step appends sample_quality() to <base_dir>/sample_quality.jsonl; 0: none, and
         # the loop is exactly what it is without this option
         self.quality_frequency = int(quality_frequency)
+        # every spectrum_frequency-th step appends spectrum() to <base_dir>/spectrum.jsonl; 0: none, and the loop is
+        # exactly what it is without this option
+        self.spectrum_frequency = int(spectrum_frequency)
         self._eval_stack = self._eval_rows = None  # evaluate()'s kept device buffers
+        self._spectrum_buffers = None               # spectrum()'s
         self.batch_size = network.batch_size
         self.data_dims = list(dataset.data_dims)
         self.device = network.device
@@ -198,6 +202,8 @@ class NoisyTrainer:
             self.write_latent_information()
         if self.quality_frequency > 0 and self.iteration % self.quality_frequency == 0:
             self.write_sample_quality()
+        if self.spectrum_frequency > 0 and self.iteration % self.spectrum_frequency == 0:
+            self.write_spectrum()
         return loss
 
     def write_summaries(self):
@@ -255,6 +261,50 @@ class NoisyTrainer:
         return float(err) / n
 
     # ------------------------------------------------------------------ held-out evaluation
+    def _eval_windows(self, split, num_batches, seed, what):
+        """The fixed walk that evaluate(), latent_information() and spectrum() share: (data, windows, images, seed)
+        for ``split``, windows a list of (start, rows not yet counted) as evaluate() describes them.  Raises for the
+        PixelVAE head, a bad split, N < B and an empty walk."""
+        net, ds = self.network, self.dataset
+        if getattr(net.cfg, "external_generator_from", 0):
+            raise ValueError("the PixelVAE head is not a trainer network")
+        if split not in ("test", "train"):
+            raise ValueError("split must be 'test' or 'train', got %r" % (split,))
+        data = ds.test if split == "test" else ds.train
+        N, B = int(data.shape[0]), self.batch_size
+        if N < B:
+            raise ValueError("batch %d exceeds the %d images of the %s split" % (B, N, split))
+        seed = self.seed if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF
+        windows = [(s, B) for s in range(0, N - B + 1, B)]  # (start, rows not yet counted)
+        if num_batches is not None:
+            windows = windows[:max(0, int(num_batches))]
+        elif N % B:
+            windows.append((N - B, N % B))
+        images = sum(f for _, f in windows)
+        if images == 0:
+            raise ValueError("%s needs at least one window" % what)
+        return data, windows, images, seed
+
+    def _eval_forwards(self, data, windows, seed):
+        """The forwards of that walk, one per window, under evaluate()'s draws: the corruption key
+        ``seed ^ eval_seed_xor`` from offset 0, eps and then the chain noise from one
+        ``torch.Generator(device).manual_seed(seed)``, forward at reg_coeff 1.0.  Yields (input, rows not yet
+        counted) with the window's forward as the network's last one and its clean images in self._target."""
+        net = self.network
+        B, T = self.batch_size, net.cfg.mc_steps
+        H, W, C = self.data_dims
+        gen = torch.Generator(device=self.device).manual_seed(seed)
+        offset = 0
+        for start, fresh in windows:
+            inp, corrupted = self._corrupted_batch(data, start, seed ^ self.eval_seed_xor, offset)
+            offset += self._groups() if corrupted else 0
+            eps = torch.randn([T, B, net.cfg.latent_dim], generator=gen, dtype=torch.float32, device=self.device)
+            noise = None
+            if net.cfg.add_noise_to_chain:
+                noise = torch.randn([T, B, H, W, C], generator=gen, dtype=torch.float32, device=self.device)
+            net.forward(inp, self._target, eps, 1.0, noise=noise)
+            yield inp, fresh
+
     def evaluate(self, split="test", num_batches=None, seed=None):
         """Quality of every chain step on a fixed validation set: the whole ``split`` ("test" or "train"), each
         image once, scored against the clean image in PSNR and SSIM (metrics.image_metrics), with the corrupted
@@ -286,28 +336,12 @@ class NoisyTrainer:
         Afterwards the network's last forward is the evaluation's last window: summaries() reads the last
         forward, so call it before evaluating (step() does)."""
         net, ds = self.network, self.dataset
-        if getattr(net.cfg, "external_generator_from", 0):
-            raise ValueError("the PixelVAE head is not a trainer network")
-        if split not in ("test", "train"):
-            raise ValueError("split must be 'test' or 'train', got %r" % (split,))
+        data, windows, images, seed = self._eval_windows(split, num_batches, seed, "evaluate")
         from . import metrics
-        data = ds.test if split == "test" else ds.train
-        N, B, T = int(data.shape[0]), self.batch_size, net.cfg.mc_steps
+        B, T = self.batch_size, net.cfg.mc_steps
         H, W, C = self.data_dims
-        if N < B:
-            raise ValueError("batch %d exceeds the %d images of the %s split" % (B, N, split))
-        seed = self.seed if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF
-        windows = [(s, B) for s in range(0, N - B + 1, B)]  # (start, rows not yet counted)
-        if num_batches is not None:
-            windows = windows[:max(0, int(num_batches))]
-        elif N % B:
-            windows.append((N - B, N % B))
-        images = sum(f for _, f in windows)
-        if images == 0:
-            raise ValueError("evaluate needs at least one window")
         lo, hi = ds.range
         L, per = hi - lo, H * W * C
-        gen = torch.Generator(device=self.device).manual_seed(seed)
         if self._eval_stack is None:
             self._eval_stack = torch.empty([T + 1, B, H, W, C], dtype=torch.float32, device=self.device)
             self._eval_rows = torch.empty([(T + 1) * B, metrics.COLS], dtype=torch.float64, device=self.device)
@@ -316,15 +350,7 @@ class NoisyTrainer:
         table = torch.zeros([T + 1, 5], dtype=torch.float64, device=self.device)
         elbo = torch.zeros((), dtype=torch.float64, device=self.device)
         stream = _lib.stream_ptr(torch.cuda.current_stream(self.device))
-        offset = 0
-        for start, fresh in windows:
-            inp, corrupted = self._corrupted_batch(data, start, seed ^ self.eval_seed_xor, offset)
-            offset += self._groups() if corrupted else 0
-            eps = torch.randn([T, B, net.cfg.latent_dim], generator=gen, dtype=torch.float32, device=self.device)
-            noise = None
-            if net.cfg.add_noise_to_chain:
-                noise = torch.randn([T, B, H, W, C], generator=gen, dtype=torch.float32, device=self.device)
-            net.forward(inp, self._target, eps, 1.0, noise=noise)
+        for inp, fresh in self._eval_forwards(data, windows, seed):
             stack[0].copy_(inp)
             for t in range(T):
                 _lib.check(net.L.svae_copy_out(net.ctx, _lib.BUF_XHAT, t, _lib.ptr(stack[1 + t]), B * per, stream),
@@ -386,37 +412,13 @@ class NoisyTrainer:
 
         ``mi`` saturates at ``mi_ceiling`` = log(images): see latents.py.  Under use_uniform_prior prior_stddev,
         marginal_kl, kl_sample and kl are None.  Afterwards the network's last forward is the walk's last window."""
-        net, ds = self.network, self.dataset
-        if getattr(net.cfg, "external_generator_from", 0):
-            raise ValueError("the PixelVAE head is not a trainer network")
-        if split not in ("test", "train"):
-            raise ValueError("split must be 'test' or 'train', got %r" % (split,))
+        net = self.network
+        data, windows, images, seed = self._eval_windows(split, num_batches, seed, "latent_information")
         from . import latents
-        data = ds.test if split == "test" else ds.train
-        N, B, T, Dz = int(data.shape[0]), self.batch_size, net.cfg.mc_steps, net.cfg.latent_dim
-        H, W, C = self.data_dims
-        if N < B:
-            raise ValueError("batch %d exceeds the %d images of the %s split" % (B, N, split))
-        seed = self.seed if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF
-        windows = [(s, B) for s in range(0, N - B + 1, B)]  # (start, rows not yet counted)
-        if num_batches is not None:
-            windows = windows[:max(0, int(num_batches))]
-        elif N % B:
-            windows.append((N - B, N % B))
-        images = sum(f for _, f in windows)
-        if images == 0:
-            raise ValueError("latent_information needs at least one window")
-        gen = torch.Generator(device=self.device).manual_seed(seed)
+        B, T, Dz = self.batch_size, net.cfg.mc_steps, net.cfg.latent_dim
         kept = torch.empty([3, T, images, Dz], dtype=torch.float32, device=self.device)  # mu, sigma, z
-        offset = done = 0
-        for start, fresh in windows:
-            inp, corrupted = self._corrupted_batch(data, start, seed ^ self.eval_seed_xor, offset)
-            offset += self._groups() if corrupted else 0
-            eps = torch.randn([T, B, Dz], generator=gen, dtype=torch.float32, device=self.device)
-            noise = None
-            if net.cfg.add_noise_to_chain:
-                noise = torch.randn([T, B, H, W, C], generator=gen, dtype=torch.float32, device=self.device)
-            net.forward(inp, self._target, eps, 1.0, noise=noise)
+        done = 0
+        for _, fresh in self._eval_forwards(data, windows, seed):
             for k, which in enumerate((_lib.BUF_MU, _lib.BUF_SIGMA, _lib.BUF_Z)):
                 for t in range(T):
                     kept[k, t, done:done + fresh] = net.latent(which, t)[B - fresh:]
@@ -446,6 +448,21 @@ class NoisyTrainer:
         return row
 
     # ------------------------------------------------------------------ how good the samples are
+    def _generated_windows(self, nwin, seed):
+        """sample_quality()'s draws, shared with spectrum(): ``nwin`` calls of network.generate(z, noise) with z
+        [T,B,Dz] and then, under add_noise_to_chain, the chain noise [T,B,H,W,C] of every window from one
+        ``torch.Generator(device).manual_seed(seed)``.  Yields (window, [x_hat_t for every t])."""
+        net = self.network
+        B, T = self.batch_size, net.cfg.mc_steps
+        H, W, C = self.data_dims
+        gen = torch.Generator(device=self.device).manual_seed(seed)
+        for w in range(nwin):
+            z = torch.randn([T, B, net.cfg.latent_dim], generator=gen, dtype=torch.float32, device=self.device)
+            noise = None
+            if net.cfg.add_noise_to_chain:
+                noise = torch.randn([T, B, H, W, C], generator=gen, dtype=torch.float32, device=self.device)
+            yield w, net.generate(z, noise=noise)
+
     def sample_quality(self, split="test", num_batches=None, seed=None, train_images=None):
         """Per chain step, how close generated samples x_hat_t are to held-out images and whether they copy
         training images: the kernel MMD^2 two-sample estimate, the leave-one-out 1-nearest-neighbour two-sample
@@ -501,16 +518,11 @@ class NoisyTrainer:
         if M < 1 or M > int(ds.train.shape[0]) or int(ds.train.shape[0]) < B:
             raise ValueError("train_images must be in [1, %d] and the training set hold a batch" % int(ds.train.shape[0]))
         seed = self.seed if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF
-        gen = torch.Generator(device=self.device).manual_seed(seed)
         kept = torch.empty([T + 1, N, D], dtype=torch.float32, device=self.device)  # X_0 .. X_{T-1}, R
-        for w in range(nwin):
+        for w, xhats in self._generated_windows(nwin, seed):
             self._make_batch(data, w * B, self._target, None, 0, 0, noise=False)
             kept[T, w * B:(w + 1) * B] = self._target.view(B, D)
-            z = torch.randn([T, B, Dz], generator=gen, dtype=torch.float32, device=self.device)
-            noise = None
-            if net.cfg.add_noise_to_chain:
-                noise = torch.randn([T, B, H, W, C], generator=gen, dtype=torch.float32, device=self.device)
-            for t, xh in enumerate(net.generate(z, noise=noise)):
+            for t, xh in enumerate(xhats):
                 kept[t, w * B:(w + 1) * B] = xh.reshape(B, D)
         train = torch.empty([M, D], dtype=torch.float32, device=self.device)
         for start in range(0, M, B):
@@ -556,6 +568,109 @@ class NoisyTrainer:
         if self.base_dir is not None:
             os.makedirs(self.base_dir, exist_ok=True)
             with open(os.path.join(self.base_dir, "sample_quality.jsonl"), "a") as f:
+                f.write(line + "\n")
+        return row
+
+    # ------------------------------------------------------------------ at which frequencies the outputs fail
+    def spectrum(self, split="test", num_batches=None, seed=None, samples=True, window="hann"):
+        """Per chain step, the radially averaged power spectrum of the outputs x_hat_t and of their error against
+        the clean images, beside the clean images' own spectrum (spectra.power_spectrum on
+        svae_op_power_spectrum): at which spatial frequencies step t still fails, and whether its outputs and the
+        generated samples are as sharp as real images.  PSNR and SSIM both reward a smooth output; this report
+        does not.
+
+        The split is walked exactly as evaluate() walks it: the same windows (a last partial window [N - B, N) of
+        which only the rows not yet counted are kept; ``num_batches`` = k the first k whole windows), the same
+        corruption key ``seed ^ eval_seed_xor`` from offset 0, the same ``torch.Generator(device).manual_seed(seed)``
+        stream with eps drawn first and then the chain noise under add_noise_to_chain, forward at reg_coeff 1.0.
+        The report therefore describes the very forwards that evaluate(seed=...) scores, and like it moves nothing
+        of the training run: no cursor, no offset, no parameter, no Adam state, not the iteration and not the
+        device Philox counter.  It raises as evaluate() does for the PixelVAE head, N < B and a bad split.
+
+        Per window the kept [T + 1, B, H, W, C] stack (slot 0 the input, slots 1 .. T the x_hat_t) is scored
+        against the clean images in one launch and the clean images themselves in a second one (y = None); with
+        ``samples`` the whole windows are then generated again as sample_quality() draws them (z [T,B,Dz], then
+        the chain noise, from a second generator under the same seed) and scored alone.  ``window`` is "hann"
+        (periodic, the default: an image is not periodic, and without a window its edges leak into every
+        frequency) or "none".  Sums go into a device fp64 table; one device -> host copy at the end.  Returns
+
+            {"split", "images", "seed", "window", "bins", "counts", "target": {"power_db"},
+             "input": {"power_db", "band_snr_db", "log_spectral_distance", "hf_ratio", "cutoff"},
+             "steps": [{the same} for every t], "sample_images",
+             "samples": [{"power_db", "log_spectral_distance", "hf_ratio"} for every t], "nonfinite"}
+
+        with the channels summed and means over the images.  ``bins`` are the annuli's radii in cycles per pixel
+        (b / min(H, W), up to 1/2), ``counts`` their numbers of spectrum entries.  power_db[b] is 10 log10 of the
+        mean power per entry of annulus b; band_snr_db[b] = 10 log10(target power / error power) there;
+        log_spectral_distance the RMS over b >= 1 of the dB difference to the target's profile; hf_ratio the power
+        in the bins above n_bins / 2 over the target's (1: as sharp as the data, below 1: blurred); cutoff the first
+        b >= 1 whose band SNR is below 0 dB, over n_bins (1.0: none: every annulus is closer to the clean image than
+        a blank one would be).  ``nonfinite`` is the number of non-finite elements among the inputs, outputs, clean
+        images and samples that were scored, each counted once (0 in a healthy run).
+        Afterwards the network's last forward is the walk's last window, or invalid after the samples:
+        summaries() must be read before (step() does)."""
+        net = self.network
+        data, windows, images, seed = self._eval_windows(split, num_batches, seed, "spectrum")
+        from . import spectra
+        B, T = self.batch_size, net.cfg.mc_steps
+        H, W, C = self.data_dims
+        per = H * W * C
+        nb, counts = spectra.device_tables(H, W, window, self.device)[5:7]
+        f64 = dict(dtype=torch.float64, device=self.device)
+        if self._spectrum_buffers is None:  # kept like evaluate()'s: a report every k-th step allocates once
+            self._spectrum_buffers = (torch.empty([T + 1, B, H, W, C], dtype=torch.float32, device=self.device),
+                                      torch.empty([(T + 1) * B, C, 2, nb], **f64), torch.zeros([B, C, 2, nb], **f64),
+                                      torch.zeros([T + 2, B, C], dtype=torch.int64, device=self.device))
+        stack, rows, trow, bad = self._spectrum_buffers
+        table = torch.zeros([T + 1, 2, nb], **f64)   # per slot: the power and the error power, summed
+        ttable = torch.zeros([nb], **f64)            # the clean images' power
+        stable = torch.zeros([T, nb], **f64)         # the generated samples' power
+        nonfinite = torch.zeros((), dtype=torch.int64, device=self.device)
+        stream = _lib.stream_ptr(torch.cuda.current_stream(self.device))
+        for inp, fresh in self._eval_forwards(data, windows, seed):
+            stack[0].copy_(inp)
+            for t in range(T):
+                _lib.check(net.L.svae_copy_out(net.ctx, _lib.BUF_XHAT, t, _lib.ptr(stack[1 + t]), B * per, stream),
+                           net.ctx)
+            r = spectra.power_spectrum(stack, self._target, window, out=rows, nonfinite=bad[:T + 1])
+            table += r.view(T + 1, B, C, 2, nb)[:, B - fresh:].sum((1, 2))
+            tr = spectra.power_spectrum(self._target, None, window, out=trow, nonfinite=bad[T + 1])
+            ttable += tr[B - fresh:, :, 0].sum((0, 1))
+            # a stack row's count includes its partner's: the clean images count once, from their own launch
+            nonfinite += bad[:T + 1, B - fresh:].sum() - T * bad[T + 1, B - fresh:].sum()
+        sample_images = 0
+        if samples:
+            nwin = sum(1 for _, fresh in windows if fresh == B)
+            for _, xhats in self._generated_windows(nwin, seed):
+                for t, xh in enumerate(xhats):
+                    stack[1 + t].copy_(xh)
+                r = spectra.power_spectrum(stack[1:], None, window, out=rows, nonfinite=bad[:T])
+                stable += r.view(T, B, C, 2, nb)[:, :, :, 0].sum((1, 2))
+                nonfinite += bad[:T].sum()
+            sample_images = nwin * B
+        host = torch.cat([table.reshape(-1) / images, ttable / images, stable.reshape(-1) / max(sample_images, 1),
+                          nonfinite.double().reshape(1)]).cpu().tolist()
+        slot = lambda s, plane: host[(2 * s + plane) * nb:(2 * s + plane + 1) * nb]
+        target = host[2 * (T + 1) * nb:(2 * T + 3) * nb]
+        sample = lambda t: host[(2 * T + 3 + t) * nb:(2 * T + 4 + t) * nb]
+        entry = lambda s: spectra.profile_report(slot(s, 0), target, counts, err=slot(s, 1))
+        return {"split": split, "images": images, "seed": seed, "window": window,
+                "bins": [b / min(H, W) for b in range(nb)], "counts": [float(v) for v in counts],
+                "target": {"power_db": spectra.profile_report(target, target, counts)["power_db"]},
+                "input": entry(0), "steps": [entry(1 + t) for t in range(T)], "sample_images": sample_images,
+                "samples": [spectra.profile_report(sample(t), target, counts) for t in range(T)] if sample_images
+                else [], "nonfinite": int(host[-1])}
+
+    def write_spectrum(self, **kw):
+        """One line {"iteration", <spectrum(**kw)>}: logged at info level and, with a base_dir, appended to
+        <base_dir>/spectrum.jsonl (a resumed run goes on in the same file)."""
+        row = {"iteration": self.iteration}
+        row.update(self.spectrum(**kw))
+        line = json.dumps(row)
+        self.LOG.info(line)
+        if self.base_dir is not None:
+            os.makedirs(self.base_dir, exist_ok=True)
+            with open(os.path.join(self.base_dir, "spectrum.jsonl"), "a") as f:
                 f.write(line + "\n")
         return row
 

@@ -10,7 +10,9 @@ that iteration's.  The seeds come from the run's trainer.json (--synthetic image
 evaluation's draws).  Prints the result as one JSON line and writes it to eval.json next to the checkpoint.
 --latent_information reports what the latent code of those same forwards carries instead
 (NoisyTrainer.latent_information, into latent_information.json).  --sample_quality scores samples generated from
-prior latents against the split instead (NoisyTrainer.sample_quality, into sample_quality.json).
+prior latents against the split instead (NoisyTrainer.sample_quality, into sample_quality.json).  --spectrum reports
+the radially averaged power spectra of those same forwards' outputs, of their error and of generated samples
+(NoisyTrainer.spectrum, into spectrum.json).
 """
 import argparse
 import importlib
@@ -42,6 +44,11 @@ def parse(argv=None):
                     help="report NoisyTrainer.sample_quality() instead: per-step kernel MMD^2, 1-nearest-neighbour "
                          "two-sample accuracy and nearest-training-image distances of generated samples against the "
                          "split's whole windows; written to sample_quality.json")
+    ap.add_argument("--spectrum", action="store_true",
+                    help="report NoisyTrainer.spectrum() of the same forwards instead: per step the radially averaged "
+                         "power spectrum of the outputs and of their error against the clean images' own, band SNR, "
+                         "high-frequency ratio and cutoff, and the spectra of generated samples; written to "
+                         "spectrum.json")
     ap.add_argument("--dtype", default="bf16x6", choices=["fp32", "bf16", "bf16x6"])
     importlib.import_module(PKG + ".degrade").add_flags(ap)
     importlib.import_module(PKG + ".crops").add_flags(ap)
@@ -112,14 +119,16 @@ def main(argv=None):
     net.load_checkpoint(ckpt)
     trainer = NT(net, ds, denoise_train=a.denoise_train, seed=run_seed, degradation=degradation(a))
     row = {"iteration": int(state.get("iteration", net.iteration))}
-    if a.latent_information and a.sample_quality:
-        print("--latent_information and --sample_quality are two reports: ask for one")
+    if a.latent_information + a.sample_quality + a.spectrum > 1:
+        print("--latent_information, --sample_quality and --spectrum are separate reports: ask for one")
         return 1
     report, name = trainer.evaluate, "eval.json"
     if a.latent_information:
         report, name = trainer.latent_information, "latent_information.json"
     if a.sample_quality:
         report, name = trainer.sample_quality, "sample_quality.json"
+    if a.spectrum:
+        report, name = trainer.spectrum, "spectrum.json"
     row.update(report(split=a.split, num_batches=a.num_batches, seed=a.seed))
     line = json.dumps(row)
     with open(os.path.join(base_dir, name), "w") as f:

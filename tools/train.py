@@ -48,6 +48,10 @@ def parse(argv=None):
                     help="append NoisyTrainer.sample_quality() against the test split (per-step kernel MMD^2, "
                          "1-nearest-neighbour two-sample accuracy and nearest-training-image distances of generated "
                          "samples) to <model dir>/sample_quality.jsonl every N iterations (0: off)")
+    ap.add_argument("--spectrum_frequency", type=int, default=0,
+                    help="append NoisyTrainer.spectrum() of the test split (per-step radially averaged power spectra "
+                         "of the outputs, their error and the generated samples against the clean images' own) to "
+                         "<model dir>/spectrum.jsonl every N iterations (0: off)")
     ap.add_argument("--iters", type=int, default=None, help="iterations to run (default: the reference's 10^7)")
     ap.add_argument("--dtype", default="bf16x6", choices=["fp32", "bf16", "bf16x6"])
     importlib.import_module(PKG + ".degrade").add_flags(ap)
@@ -128,7 +132,7 @@ def main(argv=None):
                  plot_reconstruction=a.plot_reconstruction, base_dir=base_dir, logger=log, seed=a.seed,
                  summary_freq=a.summary_freq, eval_frequency=a.eval_frequency,
                  info_frequency=a.info_frequency, quality_frequency=a.quality_frequency,
-                 degradation=degradation(a))
+                 degradation=degradation(a), spectrum_frequency=a.spectrum_frequency)
     if a.continue_training and os.path.exists(os.path.join(base_dir, "trainer.json")):
         trainer.load(base_dir)
         log.info("resumed at iteration %d" % trainer.iteration)
