@@ -204,6 +204,20 @@ int svae_adam_range(svae_ctx* ctx, int64_t lo, int64_t hi, float lr, int64_t ste
  * returns -- and the recognition bucket after hook(user, -1).  Shared weights: the two calls in
  * sequence. */
 int svae_backward_adam(svae_ctx* ctx, float lr, int64_t step, float clip, void* stream);
+/* Polyak (exponential moving) average of the parameters, TF's ExponentialMovingAverage.apply.  ema is a
+ * caller-owned device buffer of n_total floats in the public layout, borrowed until changed; omd = 1 - decay_t in
+ * [0, 1].  Sticky: ema == NULL or omd == 0 turns it off, and with it off no launch is made.  While on, every Adam
+ * update of a live range [lo, hi) (svae_adam, svae_adam_range, the buckets of svae_backward_adam, svae_adam_imp) is
+ * followed on the same stream by svae_op_ema(ema + lo, params + lo, hi - lo, omd): under svae_backward_adam a
+ * bucket's average moves on the side stream as soon as that bucket's Adam is done.  One training step therefore
+ * averages every live parameter exactly once, after its last update.  With a gradient buffer bound by
+ * svae_bind_imp the recognition range [0, phi_end) gets two updates per step, so svae_adam, svae_adam_range and
+ * svae_backward_adam leave that range of the average alone and svae_adam_imp averages it after its own update (a
+ * caller that never calls svae_adam_imp never averages it).  Parameters, Adam moments and the bf16 / fp16 weight
+ * copies are bit for bit what they are with averaging off.  The dead tail [n_live, n_total) of ema is never
+ * written: the caller initialises it (a copy of the parameters).  SVAE_EBADARG: null ctx, omd outside [0, 1] or
+ * NaN. */
+int svae_set_ema(svae_ctx* ctx, float* ema, float omd);
 /* Adam moments of the live region [0, n_live) (tf.train.Saver's "<var>/Adam", "<var>/Adam_1" slots,
  * abstract_network.py:124-152): dir 0 copies them out to m, v; dir 1 in.  Device pointers. */
 int svae_adam_state(svae_ctx* ctx, int dir, float* m, float* v, int64_t n, void* stream);
@@ -715,6 +729,15 @@ int svae_op_pairwise_stats(const float* x, int64_t n, int64_t ldx, const float* 
 int svae_op_power_spectrum(const float* x, int n, const float* y, int ny, int h, int w, int c, const double* win_y,
                            const double* win_x, const double* tw_y, const double* tw_x, const int32_t* bin, int n_bins,
                            double* out, int64_t* nonfinite, void* stream);
+
+/* The averaging kernel alone (csrc/ema.hip): ema[i] = ema[i] - omd * (ema[i] - w[i]) for i in [0, n), one launch
+ * on `stream`, no allocation, no synchronisation.  The inner difference, the product and the outer difference are
+ * each rounded to fp32 once (no fused multiply-add): bitwise a numpy float32 restatement, whatever the grid and
+ * whatever the alignment of either pointer (16-byte accesses from the first 16-byte boundary of ema, on w too when
+ * it is aligned there; element by element before and after).  A NaN or inf in w or ema propagates as the formula
+ * says.  ema and w must not overlap.  omd == 0 makes no launch.  SVAE_EBADARG: a null pointer, n <= 0, omd outside
+ * [0, 1] or NaN. */
+int svae_op_ema(float* ema, const float* w, int64_t n, float omd, void* stream);
 
 #ifdef __cplusplus
 }

@@ -204,6 +204,8 @@ def _load(path):
         "svae_backward_imp": ([vp, vp], i32),
         "svae_adam_imp": ([vp, f32, i64, f32, vp], i32),
         "svae_imp_range": ([vp, ctypes.POINTER(i64)], i32),
+        "svae_set_ema": ([vp, vp, f32], i32),
+        "svae_op_ema": ([vp, vp, i64, f32, vp], i32),
         # PixelCNN++ head (include/svae_pcnn.h)
         "svae_pcnn_wnorm": ([vp, vp, i32, i32, i32, vp, vp, i32, vp, i32, vp], i32),
         "svae_pcnn_wnorm_bwd": ([vp, vp, vp, vp, i32, i32, i32, vp, vp, vp], i32),
@@ -272,7 +274,7 @@ EXPORTED = ["svae_param_count", "svae_param_layout", "svae_create", "svae_destro
             "svae_op_dense_bf16", "svae_op_fc_wgrad", "svae_op_image_metrics",
             "svae_op_mixture_logdensity", "svae_op_pairwise_scratch_bytes", "svae_op_pairwise_stats",
             "svae_op_degrade_batch", "svae_op_extract_tiles", "svae_op_blend_tiles", "svae_op_crop_batch",
-            "svae_op_jpeg_batch", "svae_rng_offset", "svae_op_power_spectrum"]
+            "svae_op_jpeg_batch", "svae_rng_offset", "svae_op_power_spectrum", "svae_set_ema", "svae_op_ema"]
 # include/svae_pcnn.h (the PixelCNN++ head)
 PCNN_EXPORTED = ["svae_pcnn_wnorm", "svae_pcnn_wnorm_bwd", "svae_pcnn_conv", "svae_pcnn_conv_wgrad", "svae_pcnn_colsum",
                  "svae_pcnn_colsum_absmax", "svae_pcnn_im2col_h16", "svae_pcnn_conv_planes_amax",

@@ -606,6 +606,10 @@ struct svae_ctx {
   int share_nseg = 0, share_ntab = 0;
   float* adam_m = nullptr;
   float* adam_v = nullptr;
+  // svae_set_ema: the caller's averages (public layout) and 1 - decay_t; ema_imp: inside svae_adam_imp
+  float* ema = nullptr;
+  float ema_omd = 0.f;
+  bool ema_imp = false;
   char* arena = nullptr;
   size_t arena_bytes = 0, arena_used = 0;
   hipStream_t st = 0;
@@ -3243,6 +3247,20 @@ static void adam_range(svae_ctx* c, long long lo, long long hi, float lr, long l
                    c->wtab);
     c->fresh += hi - lo;
   }
+  if (c->ema) {
+    // every parameter once per step, after its last update: with the improvement loss bound the recognition
+    // range belongs to svae_adam_imp's pass
+    const long long elo = (c->Gimp_pub && !c->ema_imp) ? std::max(lo, c->m.p_phi_end) : lo;
+    if (elo < hi) ema_update(c->ema + elo, c->Ppub + elo, hi - elo, c->ema_omd, s);
+  }
+}
+
+int svae_set_ema(svae_ctx* c, float* ema, float omd) {
+  if (!c) return fail(c, SVAE_EBADARG, "null ctx");
+  if (!(omd >= 0.f && omd <= 1.f)) return fail(c, SVAE_EBADARG, "set_ema: omd must be in [0, 1]");
+  c->ema = (ema && omd > 0.f) ? ema : nullptr;
+  c->ema_omd = c->ema ? omd : 0.f;
+  return 0;
 }
 
 int svae_adam(svae_ctx* c, float lr, int64_t step, float clip, void* stream) {
@@ -3283,7 +3301,9 @@ int svae_adam_imp(svae_ctx* c, float lr, int64_t step, float clip, void* stream)
   float* gp = c->Gpub;
   const long long f0 = c->fresh;  // re-refreshes shadows the ELBO update already counted
   c->Gpub = c->Gimp_pub;
+  c->ema_imp = true;
   adam_range(c, 0, c->m.p_phi_end, lr, step, clip, (hipStream_t)stream);
+  c->ema_imp = false;
   c->Gpub = gp;
   c->fresh = f0;
   HIPCHK(c, hipGetLastError());
@@ -3356,6 +3376,16 @@ int svae_copy_out(svae_ctx* c, int which, int step, float* dst, int64_t n, void*
   }
   HIPCHK(c, hipMemcpyAsync(dst, src, cnt * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return 0;
+}
+
+int svae_op_ema(float* ema, const float* w, int64_t n, float omd, void* stream) {
+  if (!ema || !w) return fail(nullptr, SVAE_EBADARG, "ema: null pointer");
+  if (n <= 0) return fail(nullptr, SVAE_EBADARG, "ema: n must be positive");
+  if (!(omd >= 0.f && omd <= 1.f)) return fail(nullptr, SVAE_EBADARG, "ema: omd must be in [0, 1]");
+  if (omd == 0.f) return 0;
+  ema_update(ema, w, n, omd, (hipStream_t)stream);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
 }
 
 }  // extern "C"

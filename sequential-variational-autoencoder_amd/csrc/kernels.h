@@ -446,6 +446,9 @@ void pairwise_stats(const float* x, long long n, long long ldx, const float* con
 hipError_t power_spectrum(const float* x, int n, const float* y, int ny, int h, int w, int c, const double* win_y,
                           const double* win_x, const double* tw_y, const double* tw_x, const int* bin, int n_bins,
                           double* out, long long* nonfinite, hipStream_t s);
+// ---- Polyak average (ema.hip): ema[i] -= omd * (ema[i] - w[i]) over [0, n), three fp32 roundings, one launch on s
+// (none for n <= 0 or omd == 0); any alignment of either pointer ----
+void ema_update(float* ema, const float* w, long long n, float omd, hipStream_t s);
 // column sums of X [rows][C<=4] -> out0[0..n0), out1[0..C-n0)   (part: scratch >= 1024 floats)
 void colsum_small(const float* X, int ld, long long rows, int C, float* part, float* out0, int n0, float* out1,
                   hipStream_t s);

@@ -25,9 +25,11 @@ from .weights import init_flat, param_table, unflatten
 
 
 class SequentialVAE:
-    def __init__(self, config="celeba", batch_size=None, device=None, seed=0, grad_hook=None, share_params_with=None):
+    def __init__(self, config="celeba", batch_size=None, device=None, seed=0, grad_hook=None, share_params_with=None,
+                 averaged=False):
         """share_params_with: another SequentialVAE whose ``params`` tensor this context reads (sibling());
-        the networks must agree in everything but the batch."""
+        the networks must agree in everything but the batch.  averaged: read that network's ``ema`` tensor
+        instead (averaged())."""
         if not torch.cuda.is_available():
             raise RuntimeError("SequentialVAE (HIP engine) needs a GPU; no CPU fallback exists")
         cfg = preset(config) if isinstance(config, str) else config
@@ -47,12 +49,20 @@ class SequentialVAE:
         self._by_name = {p["name"]: p for p in self.table}
         self._owner = share_params_with
         self._siblings = {}
+        self._averaged = bool(averaged)  # this context's ``params`` is its owner's ``ema`` tensor
+        self._averaged_ctx = {}          # the owner's averaged() contexts, per batch
+        # Polyak averaging (enable_ema): the averages [n_total] and the schedule's state
+        self.ema = None
+        self.ema_decay, self.ema_warmup, self.ema_every, self.ema_updates = None, True, 1, 0
+        self.ema_from_checkpoint = False  # the last load_checkpoint found averages in the file
+        if averaged and (share_params_with is None or share_params_with.ema is None):
+            raise ValueError("an averaged context reads the averages of a network that has them (enable_ema)")
         if self._owner is not None and (preset_copy(self._owner.cfg, batch=cfg.batch) != cfg
                                         or self._owner.device != self.device):
             raise ValueError("a sibling differs from its owner in the batch only")
         with torch.cuda.device(self.device):
             self.params = (torch.from_numpy(init_flat(cfg, seed)).to(self.device) if self._owner is None
-                           else self._owner.params)
+                           else self._owner.ema if averaged else self._owner.params)
             self.grads = torch.zeros(self.n_total, dtype=torch.float32, device=self.device)
             h = ctypes.c_void_p()
             c = cfg.to_c()
@@ -76,6 +86,8 @@ class SequentialVAE:
 
     # ------------------------------------------------------------------ lifecycle
     def close(self):
+        for a in list(getattr(self, "_averaged_ctx", {}).values()):
+            a.close()
         if getattr(self, "ctx", None):
             self.L.svae_destroy(self.ctx)
             self.ctx = None
@@ -298,6 +310,62 @@ class SequentialVAE:
         are zeroed as by svae_bind."""
         _lib.check(self.L.svae_bind(self.ctx, _lib.ptr(self.params), _lib.ptr(self.grads)), self.ctx)
 
+    # ------------------------------------------------------------------ Polyak averaging
+    def enable_ema(self, decay=0.999, warmup=True, every=1):
+        """Keep an exponential moving average of the parameters (tf.train.ExponentialMovingAverage, which the
+        reference applies to its PixelCNN alone, pixel_cnn/pixelvae.py:113-114): ``ema`` [n_total], a copy of
+        ``params`` as they stand, updated by the engine right behind every Adam update of train() (svae_set_ema,
+        csrc/ema.hip) as e -= (1 - decay_t) * (e - w).
+
+        On a step with ``iteration % every == 0`` decay_t = min(decay, (1 + n) / (10 + n)) with n = ema_updates
+        when ``warmup`` is on (TF's num_updates rule), else ``decay``; the engine gets
+        float32(1 - decay_t ** every), so that ``every`` = k averages a k-th of the steps at the same horizon.
+        Other steps make no launch.  Training itself is bit for bit what it is without averaging.  Only an owner
+        context averages; read the averages through averaged()."""
+        if self._owner is not None:
+            raise RuntimeError("a sibling context only reads its owner's parameters; enable averaging on the owner")
+        decay, every = float(decay), int(every)
+        if not 0.0 <= decay < 1.0 or every < 1:
+            raise ValueError("enable_ema needs 0 <= decay < 1 and every >= 1")
+        with torch.cuda.device(self.device):
+            self.ema = self.params.clone()
+        self.ema_decay, self.ema_warmup, self.ema_every, self.ema_updates = decay, bool(warmup), every, 0
+        for ctx in self._averaged_ctx.values():  # contexts of an earlier enable_ema read the old tensor
+            ctx.close()
+        self._averaged_ctx = {}
+        return self.ema
+
+    def ema_omd(self):
+        """1 - decay_t ** every of an averaging step taken now (n = ema_updates), as the float32 the engine gets."""
+        d = self.ema_decay
+        if self.ema_warmup:
+            d = min(d, (1.0 + self.ema_updates) / (10.0 + self.ema_updates))
+        return float(np.float32(1.0 - d ** self.ema_every))
+
+    def _arm_ema(self):
+        """train(): arm the engine for this iteration's updates (omd on an averaging step, 0 on the others)."""
+        on = self.iteration % self.ema_every == 0
+        _lib.check(self.L.svae_set_ema(self.ctx, _lib.ptr(self.ema), self.ema_omd() if on else 0.0), self.ctx)
+        self.ema_updates += 1 if on else 0
+
+    def averaged(self, batch_size=None):
+        """A context like sibling() (its own gradients and arena, cached per batch, default this network's batch)
+        whose ``params`` is this network's ``ema`` tensor: forward, generate, test, restore and the trainer's
+        reports on the averaged weights, while the training context's last forward stays what it was.  It
+        announces its parameters before every forward / generate and cannot train.  Raises without
+        enable_ema()."""
+        owner = self if self._owner is None else self._owner
+        if owner.ema is None:
+            raise RuntimeError("averaging is not enabled (enable_ema)")
+        bs = owner.cfg.batch if batch_size is None else int(batch_size)
+        a = owner._averaged_ctx.get(bs)
+        if a is None:
+            a = SequentialVAE(preset_copy(owner.cfg, batch=bs), device=owner.device.index, share_params_with=owner,
+                              averaged=True)
+            a.name = owner.name
+            owner._averaged_ctx[bs] = a
+        return a
+
     # ------------------------------------------------------------------ reference API
     def train(self, input_batch, batch_target, eps=None, noise=None):
         """One training update; returns the final-step reconstruction loss per pixel
@@ -308,10 +376,16 @@ class SequentialVAE:
         pred_latent_train_op) (:1316): two apply_gradients of one AdamOptimizer, both on gradients of
         the same forward.  TF leaves their order open; here the ELBO update (all variables, Adam step
         2k-1) runs first and the improvement update (recognition variables, step 2k) second, sharing
-        the Adam moments, so beta1_power advances twice per iteration as in TF."""
+        the Adam moments, so beta1_power advances twice per iteration as in TF.
+
+        With enable_ema() the engine is armed before the update (_arm_ema) and averages every live parameter
+        once, after its last Adam update of the step.  backward_apply / apply_gradients / apply_imp_gradients
+        called by hand use whatever the last train() armed."""
         if self._owner is not None:
             raise RuntimeError("a sibling context only reads its owner's parameters; train the owner")
         self.iteration += 1
+        if self.ema is not None:
+            self._arm_ema()
         self.learning_rate *= self.cfg.learning_rate_decay
         reg = 1.0 - math.exp(-self.iteration / self.cfg.reg_coeff_rate)
         self.forward(input_batch, batch_target, eps, reg, noise=noise)
@@ -339,7 +413,9 @@ class SequentialVAE:
         """Training state under the reference's names (tf.train.Saver, abstract_network.py:124-135):
         every variable, the Adam slots "<name>/Adam" and "<name>/Adam_1" of the tensors on the
         executed path, "beta1_power" / "beta2_power", and iteration / learning_rate as metadata
-        (which the reference does not restore).  safetensors file."""
+        (which the reference does not restore).  With enable_ema() also
+        "<name>/ExponentialMovingAverage" of those tensors and ema_decay / ema_warmup / ema_every / ema_updates
+        as metadata.  safetensors file."""
         from safetensors.torch import save_file
         m, v = self._adam_state()
         torch.cuda.synchronize(self.device)
@@ -357,20 +433,35 @@ class SequentialVAE:
         out["beta2_power"] = torch.tensor(0.999 ** (self.adam_updates + 1), dtype=torch.float32)
         rng = ctypes.c_uint64()
         _lib.check(self.L.svae_rng_offset(self.ctx, None, ctypes.byref(rng)), self.ctx)
-        save_file(out, path, metadata={"iteration": str(self.iteration), "learning_rate": repr(self.learning_rate),
-                                       "adam_updates": str(self.adam_updates), "config": self.name,
-                                       "rng_offset": str(rng.value)})
+        meta = {"iteration": str(self.iteration), "learning_rate": repr(self.learning_rate),
+                "adam_updates": str(self.adam_updates), "config": self.name, "rng_offset": str(rng.value)}
+        if self.ema is not None:  # TF's slot name; the variables Adam never touches have no average either
+            E = self.ema.cpu()
+            for p in self.table:
+                a, b = p["offset"], p["offset"] + p["size"]
+                if b <= self.n_live:
+                    out[p["name"] + "/ExponentialMovingAverage"] = E[a:b].reshape(p["shape"]).clone()
+            meta.update(ema_decay=repr(self.ema_decay), ema_warmup=str(int(self.ema_warmup)),
+                        ema_every=str(self.ema_every), ema_updates=str(self.ema_updates))
+        save_file(out, path, metadata=meta)
 
     def load_checkpoint(self, path):
         """Restore save_checkpoint's state (init_network's restore, abstract_network.py:139-152);
-        every variable must be present with its shape."""
+        every variable must be present with its shape.  A network with enable_ema() also restores the averages
+        and ema_updates (the schedule stays the one enable_ema set); from a file without averages ``ema`` becomes
+        the loaded parameters and ema_updates 0 (ema_from_checkpoint tells which).  A network without averaging
+        ignores those keys."""
         from safetensors import safe_open
         P = self.params.cpu()
         M = torch.zeros(self.n_live, dtype=torch.float32)
         V = torch.zeros(self.n_live, dtype=torch.float32)
+        E = None
         with safe_open(path, framework="pt") as f:
             meta = f.metadata() or {}
             keys = set(f.keys())
+            has_ema = any(k.endswith("/ExponentialMovingAverage") for k in keys)
+            if self.ema is not None and has_ema:
+                E = {}
             for p in self.table:
                 a, b = p["offset"], p["offset"] + p["size"]
                 if p["name"] not in keys:
@@ -382,7 +473,18 @@ class SequentialVAE:
                 if b <= self.n_live and p["name"] + "/Adam" in keys:
                     M[a:b] = f.get_tensor(p["name"] + "/Adam").reshape(-1)
                     V[a:b] = f.get_tensor(p["name"] + "/Adam_1").reshape(-1)
+                if E is not None and p["name"] + "/ExponentialMovingAverage" in keys:
+                    E[a] = f.get_tensor(p["name"] + "/ExponentialMovingAverage").reshape(-1)
+        if E is not None:  # a variable without a stored average (the frozen tail) averages to itself
+            avg = P.clone()
+            for a, t in E.items():
+                avg[a:a + t.numel()] = t
+            E = avg
         self.params.copy_(P.to(self.device))
+        if self.ema is not None:
+            self.ema.copy_((P if E is None else E).to(self.device))
+            self.ema_updates = int(meta.get("ema_updates", 0)) if E is not None else 0
+            self.ema_from_checkpoint = E is not None
         self._adam_state(M.to(self.device), V.to(self.device))
         self.params_updated()  # caller-written parameters: rebuild the engine's bf16 copies
         torch.cuda.synchronize(self.device)
@@ -441,7 +543,7 @@ class SequentialVAE:
         return self.xhat(-1).cpu().numpy()
 
     def restore(self, images, range=(-1.0, 1.0), stride=None, steps=-1, seed=None, known=None, as_uint8=None,
-                max_bytes=4 << 30):
+                max_bytes=4 << 30, weights="train"):
         """Apply the network to whole images of any size: overlapping tiles of the network's own h x w go through
         the chain and are blended back with a triangular window (restore.py, csrc/tiles.hip).
 
@@ -471,9 +573,14 @@ class SequentialVAE:
         torch.Generator(device).manual_seed(k), as evaluate() does.  Every draw is injected, so nothing of a
         training run moves: not the parameters, the Adam state or the iteration, and not the device Philox
         counter.  Afterwards the network's last forward is the last window: summaries() reads the last forward,
-        so call it before restoring.  The PixelVAE head raises as in evaluate()."""
+        so call it before restoring.  The PixelVAE head raises as in evaluate().
+
+        ``weights`` = "ema" restores through averaged() (the Polyak averages of enable_ema) and leaves this
+        context's last forward alone."""
+        if weights not in ("train", "ema"):
+            raise ValueError("weights must be 'train' or 'ema', got %r" % (weights,))
         from . import restore as _restore
-        return _restore.restore(self, images, range=range, stride=stride, steps=steps, seed=seed, known=known,
+        return _restore.restore(self if weights == "train" else self.averaged(), images, range=range, stride=stride, steps=steps, seed=seed, known=known,
                                 as_uint8=as_uint8, max_bytes=max_bytes)
 
     # ------------------------------------------------------------------ siblings / visualisation
@@ -489,6 +596,8 @@ class SequentialVAE:
         testing at another batch must see the parameters training has reached.  Cached per batch; a
         sibling does not train."""
         owner = self if self._owner is None else self._owner
+        if self._averaged:  # the averaged weights at another batch
+            return owner.averaged(batch_size)
         if batch_size == owner.cfg.batch:
             return owner
         s = owner._siblings.get(batch_size)

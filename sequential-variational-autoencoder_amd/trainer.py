@@ -48,7 +48,8 @@ class NoisyTrainer:
 
     def __init__(self, network, dataset, denoise_train=False, vis_frequency=1000, plot_reconstruction=False,
                  base_dir=None, logger=None, seed=0, summary_freq=0, eval_frequency=0, info_frequency=0,
-                 quality_frequency=0, degradation=None, spectrum_frequency=0):
+                 quality_frequency=0, degradation=None, spectrum_frequency=0, ema_decay=None, ema_warmup=True,
+                 ema_every=1):
         if list(dataset.data_dims) != list(network.data_dims):
             raise ValueError("dataset images %s, network %s" % (dataset.data_dims, network.data_dims))
         if tuple(dataset.range) != tuple(float(v) for v in network.cfg.range):
@@ -57,6 +58,14 @@ class NoisyTrainer:
             raise ValueError("the PixelVAE head is not a trainer network")
         self.network = network
         self.dataset = dataset
+        # ema_decay: the network keeps Polyak averages of its weights (SequentialVAE.enable_ema), every report takes
+        # weights="ema" and the periodic writers report both; None: every launch is exactly what it is without it
+        if ema_decay is not None:
+            if network.ema is None:
+                network.enable_ema(ema_decay, ema_warmup, ema_every)
+            elif network.ema_decay != float(ema_decay):
+                raise ValueError("the network averages with decay %r, the trainer asks for %r"
+                                 % (network.ema_decay, float(ema_decay)))
         self.denoise_train = bool(denoise_train)
         # a degrade.Degradation: every training, test and evaluation input is the clean batch blurred, down-sampled
         # and cut out by svae_op_degrade_batch (csrc/degrade.hip), then given the pixel noise (under denoise_train);
@@ -239,13 +248,14 @@ class NoisyTrainer:
                 self.save(self.base_dir)
         return loss
 
-    def test(self, epoch, num_iters=None):
+    def test(self, epoch, num_iters=None, weights="train"):
         """Mean over num_iters test batches of sum((recon - clean)^2) / (H W) / B (trainer.py:131), recon
         = training_mles[-1] of forward(noisy, clean).  The engine already reduces mean((mle - target)^2)
         per image (SVAE_BUF_REC_IMG[T-1]), so only B floats are read per batch; under
-        predict_generator_noise that buffer holds the NLL and the error is formed from x_hat."""
+        predict_generator_noise that buffer holds the NLL and the error is formed from x_hat.  ``weights`` =
+        "ema" runs the same batches on the averaged weights (network.averaged())."""
         n = self.test_num_iters if num_iters is None else int(num_iters)
-        net = self.network
+        net = self._net(weights)
         H, W, C = self.data_dims
         T = net.cfg.mc_steps
         err = torch.zeros((), dtype=torch.float64, device=self.device)
@@ -261,6 +271,38 @@ class NoisyTrainer:
         return float(err) / n
 
     # ------------------------------------------------------------------ held-out evaluation
+    def _net(self, weights):
+        """The context a report runs on: the training network, or for weights="ema" its averaged() context (its own
+        arena: the training context's last forward, like everything else of the run, stays what it was)."""
+        if weights not in ("train", "ema"):
+            raise ValueError("weights must be 'train' or 'ema', got %r" % (weights,))
+        return self.network if weights == "train" else self.network.averaged()
+
+    def _tag(self, res, weights):
+        """A report's dict with "weights" ("train" or "ema") added when the network averages; without averaging
+        the dict is exactly what it was before the option existed."""
+        if self.network.ema is not None:
+            res["weights"] = weights
+        return res
+
+    def _write_report(self, report, fname, kw):
+        """One line {"iteration", <report(**kw)>} logged at info level and, with a base_dir, appended to
+        <base_dir>/<fname>; with averaging on and no ``weights`` asked for, one line for the training weights and one
+        for the averaged ones.  Returns the first row."""
+        which = [kw["weights"]] if "weights" in kw else ["train", "ema"] if self.network.ema is not None else ["train"]
+        rows = []
+        for w in which:
+            row = {"iteration": self.iteration}
+            row.update(report(**dict(kw, weights=w)))
+            line = json.dumps(row)
+            self.LOG.info(line)
+            if self.base_dir is not None:
+                os.makedirs(self.base_dir, exist_ok=True)
+                with open(os.path.join(self.base_dir, fname), "a") as f:
+                    f.write(line + "\n")
+            rows.append(row)
+        return rows[0]
+
     def _eval_windows(self, split, num_batches, seed, what):
         """The fixed walk that evaluate(), latent_information() and spectrum() share: (data, windows, images, seed)
         for ``split``, windows a list of (start, rows not yet counted) as evaluate() describes them.  Raises for the
@@ -285,12 +327,13 @@ class NoisyTrainer:
             raise ValueError("%s needs at least one window" % what)
         return data, windows, images, seed
 
-    def _eval_forwards(self, data, windows, seed):
+    def _eval_forwards(self, data, windows, seed, net=None):
         """The forwards of that walk, one per window, under evaluate()'s draws: the corruption key
         ``seed ^ eval_seed_xor`` from offset 0, eps and then the chain noise from one
         ``torch.Generator(device).manual_seed(seed)``, forward at reg_coeff 1.0.  Yields (input, rows not yet
-        counted) with the window's forward as the network's last one and its clean images in self._target."""
-        net = self.network
+        counted) with the window's forward as the network's last one and its clean images in self._target.
+        ``net``: the context that runs them (default the training network; _net)."""
+        net = self.network if net is None else net
         B, T = self.batch_size, net.cfg.mc_steps
         H, W, C = self.data_dims
         gen = torch.Generator(device=self.device).manual_seed(seed)
@@ -305,7 +348,7 @@ class NoisyTrainer:
             net.forward(inp, self._target, eps, 1.0, noise=noise)
             yield inp, fresh
 
-    def evaluate(self, split="test", num_batches=None, seed=None):
+    def evaluate(self, split="test", num_batches=None, seed=None, weights="train"):
         """Quality of every chain step on a fixed validation set: the whole ``split`` ("test" or "train"), each
         image once, scored against the clean image in PSNR and SSIM (metrics.image_metrics), with the corrupted
         input as the baseline.
@@ -334,8 +377,12 @@ class NoisyTrainer:
         sum (x_hat_{T-1} - x)^2 / (H W) (trainer.py:131), elbo the per-image loss at reg_coeff 1.0.
 
         Afterwards the network's last forward is the evaluation's last window: summaries() reads the last
-        forward, so call it before evaluating (step() does)."""
-        net, ds = self.network, self.dataset
+        forward, so call it before evaluating (step() does).
+
+        ``weights`` = "ema" scores the Polyak averages instead (network.averaged(), with enable_ema / ema_decay):
+        the same windows, seeds and injected draws on a context of its own, so that not even the training
+        context's last forward moves.  On a network that averages the result carries "weights" (_tag)."""
+        net, ds = self._net(weights), self.dataset
         data, windows, images, seed = self._eval_windows(split, num_batches, seed, "evaluate")
         from . import metrics
         B, T = self.batch_size, net.cfg.mc_steps
@@ -350,7 +397,7 @@ class NoisyTrainer:
         table = torch.zeros([T + 1, 5], dtype=torch.float64, device=self.device)
         elbo = torch.zeros((), dtype=torch.float64, device=self.device)
         stream = _lib.stream_ptr(torch.cuda.current_stream(self.device))
-        for inp, fresh in self._eval_forwards(data, windows, seed):
+        for inp, fresh in self._eval_forwards(data, windows, seed, net):
             stack[0].copy_(inp)
             for t in range(T):
                 _lib.check(net.L.svae_copy_out(net.ctx, _lib.BUF_XHAT, t, _lib.ptr(stack[1 + t]), B * per, stream),
@@ -371,23 +418,16 @@ class NoisyTrainer:
                           "recon": mean(1 + t, 3), "kl": mean(1 + t, 4)} for t in range(T)]}
         res["error_per_pixel"] = res["steps"][-1]["mse"] * C  # sum / (H W) = mse * C
         res["elbo"] = host[-1]
-        return res
+        return self._tag(res, weights)
 
     def write_evaluation(self, **kw):
         """One line {"iteration", <evaluate(**kw)>}: logged at info level and, with a base_dir, appended to
-        <base_dir>/evaluation.jsonl (a resumed run goes on in the same file)."""
-        row = {"iteration": self.iteration}
-        row.update(self.evaluate(**kw))
-        line = json.dumps(row)
-        self.LOG.info(line)
-        if self.base_dir is not None:
-            os.makedirs(self.base_dir, exist_ok=True)
-            with open(os.path.join(self.base_dir, "evaluation.jsonl"), "a") as f:
-                f.write(line + "\n")
-        return row
+        <base_dir>/evaluation.jsonl (a resumed run goes on in the same file).  With averaging on and no ``weights``
+        given, a second line reports the averaged weights (_write_report); the first row is returned."""
+        return self._write_report(self.evaluate, "evaluation.jsonl", kw)
 
     # ------------------------------------------------------------------ what the latent code carries
-    def latent_information(self, split="test", num_batches=None, seed=None):
+    def latent_information(self, split="test", num_batches=None, seed=None, weights="train"):
         """Per chain step, how much information the latent code carries about the image and how far the aggregate
         posterior is from the prior (latents.information: mutual information, marginal KL, total correlation,
         active units), for the whole code, every ladder level and every single dimension.
@@ -411,14 +451,15 @@ class NoisyTrainer:
              "nonfinite"}
 
         ``mi`` saturates at ``mi_ceiling`` = log(images): see latents.py.  Under use_uniform_prior prior_stddev,
-        marginal_kl, kl_sample and kl are None.  Afterwards the network's last forward is the walk's last window."""
-        net = self.network
+        marginal_kl, kl_sample and kl are None.  Afterwards the network's last forward is the walk's last window.
+        ``weights`` as in evaluate(), and so is the "weights" field."""
+        net = self._net(weights)
         data, windows, images, seed = self._eval_windows(split, num_batches, seed, "latent_information")
         from . import latents
         B, T, Dz = self.batch_size, net.cfg.mc_steps, net.cfg.latent_dim
         kept = torch.empty([3, T, images, Dz], dtype=torch.float32, device=self.device)  # mu, sigma, z
         done = 0
-        for _, fresh in self._eval_forwards(data, windows, seed):
+        for _, fresh in self._eval_forwards(data, windows, seed, net):
             for k, which in enumerate((_lib.BUF_MU, _lib.BUF_SIGMA, _lib.BUF_Z)):
                 for t in range(T):
                     kept[k, t, done:done + fresh] = net.latent(which, t)[B - fresh:]
@@ -430,29 +471,24 @@ class NoisyTrainer:
         host = torch.stack([latents.information(kept[2, t], mean[t], kept[1, t], lay.segments, prior)
                             for t in range(T)]).cpu().tolist()
         steps = [lay.report(row, prior is None) for row in host]
-        return {"split": split, "images": images, "seed": seed, "mi_ceiling": math.log(images), "prior_stddev": prior,
-                "steps": [{k: s[k] for k in ("all", "levels", "dims")} for s in steps],
-                "nonfinite": sum(s["nonfinite"] for s in steps)}
+        return self._tag({"split": split, "images": images, "seed": seed, "mi_ceiling": math.log(images),
+                          "prior_stddev": prior,
+                          "steps": [{k: s[k] for k in ("all", "levels", "dims")} for s in steps],
+                          "nonfinite": sum(s["nonfinite"] for s in steps)}, weights)
 
     def write_latent_information(self, **kw):
         """One line {"iteration", <latent_information(**kw)>}: logged at info level and, with a base_dir, appended
-        to <base_dir>/latent_information.jsonl (a resumed run goes on in the same file)."""
-        row = {"iteration": self.iteration}
-        row.update(self.latent_information(**kw))
-        line = json.dumps(row)
-        self.LOG.info(line)
-        if self.base_dir is not None:
-            os.makedirs(self.base_dir, exist_ok=True)
-            with open(os.path.join(self.base_dir, "latent_information.jsonl"), "a") as f:
-                f.write(line + "\n")
-        return row
+        to <base_dir>/latent_information.jsonl (a resumed run goes on in the same file).  With averaging on and no ``weights``
+        given, a second line reports the averaged weights (_write_report); the first row is returned."""
+        return self._write_report(self.latent_information, "latent_information.jsonl", kw)
 
     # ------------------------------------------------------------------ how good the samples are
-    def _generated_windows(self, nwin, seed):
+    def _generated_windows(self, nwin, seed, net=None):
         """sample_quality()'s draws, shared with spectrum(): ``nwin`` calls of network.generate(z, noise) with z
         [T,B,Dz] and then, under add_noise_to_chain, the chain noise [T,B,H,W,C] of every window from one
-        ``torch.Generator(device).manual_seed(seed)``.  Yields (window, [x_hat_t for every t])."""
-        net = self.network
+        ``torch.Generator(device).manual_seed(seed)``.  Yields (window, [x_hat_t for every t]).  ``net`` as in
+        _eval_forwards."""
+        net = self.network if net is None else net
         B, T = self.batch_size, net.cfg.mc_steps
         H, W, C = self.data_dims
         gen = torch.Generator(device=self.device).manual_seed(seed)
@@ -463,7 +499,7 @@ class NoisyTrainer:
                 noise = torch.randn([T, B, H, W, C], generator=gen, dtype=torch.float32, device=self.device)
             yield w, net.generate(z, noise=noise)
 
-    def sample_quality(self, split="test", num_batches=None, seed=None, train_images=None):
+    def sample_quality(self, split="test", num_batches=None, seed=None, train_images=None, weights="train"):
         """Per chain step, how close generated samples x_hat_t are to held-out images and whether they copy
         training images: the kernel MMD^2 two-sample estimate, the leave-one-out 1-nearest-neighbour two-sample
         accuracy and nearest-neighbour distances (quality.two_sample), all on svae_op_pairwise_stats.
@@ -495,8 +531,9 @@ class NoisyTrainer:
              "nonfinite"}
 
         with every distance a per-element RMS, sqrt(d2 / D), and sigma0 in the units of d (not per element).
-        generate invalidates the network's last training forward: summaries() must be read before (step() does)."""
-        net, ds = self.network, self.dataset
+        generate invalidates the network's last training forward: summaries() must be read before (step() does).
+        ``weights`` as in evaluate(), and so is the "weights" field."""
+        net, ds = self._net(weights), self.dataset
         if getattr(net.cfg, "external_generator_from", 0):
             raise ValueError("the PixelVAE head is not a trainer network")
         if split not in ("test", "train"):
@@ -519,7 +556,7 @@ class NoisyTrainer:
             raise ValueError("train_images must be in [1, %d] and the training set hold a batch" % int(ds.train.shape[0]))
         seed = self.seed if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF
         kept = torch.empty([T + 1, N, D], dtype=torch.float32, device=self.device)  # X_0 .. X_{T-1}, R
-        for w, xhats in self._generated_windows(nwin, seed):
+        for w, xhats in self._generated_windows(nwin, seed, net):
             self._make_batch(data, w * B, self._target, None, 0, 0, noise=False)
             kept[T, w * B:(w + 1) * B] = self._target.view(B, D)
             for t, xh in enumerate(xhats):
@@ -554,25 +591,18 @@ class NoisyTrainer:
                           "nn_accuracy": {"samples": a["x"], "real": a["y"], "all": a["all"]},
                           "nn_real": r["nn_other"], "nn_train": nn_train(t)})
         bad += int(host[T * width + 4 * T + 3])
-        return {"split": split, "images": N, "seed": seed, "sigma0": bwl[nb // 2] ** 0.5,
-                "bandwidth_scales": list(quality.SCALES), "train_images": M, "real": {"nn_train": nn_train(T)},
-                "steps": steps, "nonfinite": bad}
+        return self._tag({"split": split, "images": N, "seed": seed, "sigma0": bwl[nb // 2] ** 0.5,
+                          "bandwidth_scales": list(quality.SCALES), "train_images": M,
+                          "real": {"nn_train": nn_train(T)}, "steps": steps, "nonfinite": bad}, weights)
 
     def write_sample_quality(self, **kw):
         """One line {"iteration", <sample_quality(**kw)>}: logged at info level and, with a base_dir, appended to
-        <base_dir>/sample_quality.jsonl (a resumed run goes on in the same file)."""
-        row = {"iteration": self.iteration}
-        row.update(self.sample_quality(**kw))
-        line = json.dumps(row)
-        self.LOG.info(line)
-        if self.base_dir is not None:
-            os.makedirs(self.base_dir, exist_ok=True)
-            with open(os.path.join(self.base_dir, "sample_quality.jsonl"), "a") as f:
-                f.write(line + "\n")
-        return row
+        <base_dir>/sample_quality.jsonl (a resumed run goes on in the same file).  With averaging on and no ``weights``
+        given, a second line reports the averaged weights (_write_report); the first row is returned."""
+        return self._write_report(self.sample_quality, "sample_quality.jsonl", kw)
 
     # ------------------------------------------------------------------ at which frequencies the outputs fail
-    def spectrum(self, split="test", num_batches=None, seed=None, samples=True, window="hann"):
+    def spectrum(self, split="test", num_batches=None, seed=None, samples=True, window="hann", weights="train"):
         """Per chain step, the radially averaged power spectrum of the outputs x_hat_t and of their error against
         the clean images, beside the clean images' own spectrum (spectra.power_spectrum on
         svae_op_power_spectrum): at which spatial frequencies step t still fails, and whether its outputs and the
@@ -608,8 +638,8 @@ class NoisyTrainer:
         a blank one would be).  ``nonfinite`` is the number of non-finite elements among the inputs, outputs, clean
         images and samples that were scored, each counted once (0 in a healthy run).
         Afterwards the network's last forward is the walk's last window, or invalid after the samples:
-        summaries() must be read before (step() does)."""
-        net = self.network
+        summaries() must be read before (step() does).  ``weights`` as in evaluate(), and so is the "weights" field."""
+        net = self._net(weights)
         data, windows, images, seed = self._eval_windows(split, num_batches, seed, "spectrum")
         from . import spectra
         B, T = self.batch_size, net.cfg.mc_steps
@@ -627,7 +657,7 @@ class NoisyTrainer:
         stable = torch.zeros([T, nb], **f64)         # the generated samples' power
         nonfinite = torch.zeros((), dtype=torch.int64, device=self.device)
         stream = _lib.stream_ptr(torch.cuda.current_stream(self.device))
-        for inp, fresh in self._eval_forwards(data, windows, seed):
+        for inp, fresh in self._eval_forwards(data, windows, seed, net):
             stack[0].copy_(inp)
             for t in range(T):
                 _lib.check(net.L.svae_copy_out(net.ctx, _lib.BUF_XHAT, t, _lib.ptr(stack[1 + t]), B * per, stream),
@@ -641,7 +671,7 @@ class NoisyTrainer:
         sample_images = 0
         if samples:
             nwin = sum(1 for _, fresh in windows if fresh == B)
-            for _, xhats in self._generated_windows(nwin, seed):
+            for _, xhats in self._generated_windows(nwin, seed, net):
                 for t, xh in enumerate(xhats):
                     stack[1 + t].copy_(xh)
                 r = spectra.power_spectrum(stack[1:], None, window, out=rows, nonfinite=bad[:T])
@@ -654,25 +684,19 @@ class NoisyTrainer:
         target = host[2 * (T + 1) * nb:(2 * T + 3) * nb]
         sample = lambda t: host[(2 * T + 3 + t) * nb:(2 * T + 4 + t) * nb]
         entry = lambda s: spectra.profile_report(slot(s, 0), target, counts, err=slot(s, 1))
-        return {"split": split, "images": images, "seed": seed, "window": window,
-                "bins": [b / min(H, W) for b in range(nb)], "counts": [float(v) for v in counts],
-                "target": {"power_db": spectra.profile_report(target, target, counts)["power_db"]},
-                "input": entry(0), "steps": [entry(1 + t) for t in range(T)], "sample_images": sample_images,
-                "samples": [spectra.profile_report(sample(t), target, counts) for t in range(T)] if sample_images
-                else [], "nonfinite": int(host[-1])}
+        res = {"split": split, "images": images, "seed": seed, "window": window,
+               "bins": [b / min(H, W) for b in range(nb)], "counts": [float(v) for v in counts],
+               "target": {"power_db": spectra.profile_report(target, target, counts)["power_db"]},
+               "input": entry(0), "steps": [entry(1 + t) for t in range(T)], "sample_images": sample_images,
+               "samples": [spectra.profile_report(sample(t), target, counts) for t in range(T)] if sample_images
+               else [], "nonfinite": int(host[-1])}
+        return self._tag(res, weights)
 
     def write_spectrum(self, **kw):
         """One line {"iteration", <spectrum(**kw)>}: logged at info level and, with a base_dir, appended to
-        <base_dir>/spectrum.jsonl (a resumed run goes on in the same file)."""
-        row = {"iteration": self.iteration}
-        row.update(self.spectrum(**kw))
-        line = json.dumps(row)
-        self.LOG.info(line)
-        if self.base_dir is not None:
-            os.makedirs(self.base_dir, exist_ok=True)
-            with open(os.path.join(self.base_dir, "spectrum.jsonl"), "a") as f:
-                f.write(line + "\n")
-        return row
+        <base_dir>/spectrum.jsonl (a resumed run goes on in the same file).  With averaging on and no ``weights``
+        given, a second line reports the averaged weights (_write_report); the first row is returned."""
+        return self._write_report(self.spectrum, "spectrum.jsonl", kw)
 
     def plot_reconstruction(self, train_epoch, original_images, noisy_images, reconstructed_images, num_plot=3):
         """original | noisy | reconstruction of the first num_plot images (canvas.reconstruction_canvas);

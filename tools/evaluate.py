@@ -49,6 +49,9 @@ def parse(argv=None):
                          "power spectrum of the outputs and of their error against the clean images' own, band SNR, "
                          "high-frequency ratio and cutoff, and the spectra of generated samples; written to "
                          "spectrum.json")
+    ap.add_argument("--ema", action="store_true",
+                    help="report on the Polyak-averaged weights the run kept (tools/train.py --ema_decay) instead of "
+                         "the last step's")
     ap.add_argument("--dtype", default="bf16x6", choices=["fp32", "bf16", "bf16x6"])
     importlib.import_module(PKG + ".degrade").add_flags(ap)
     importlib.import_module(PKG + ".crops").add_flags(ap)
@@ -116,7 +119,11 @@ def main(argv=None):
     ds = dataset(a, cfg, run_seed)
     net = SV(cfg, seed=run_seed)
     net.name = a.netname
+    if a.ema:
+        net.enable_ema()  # before loading: load_checkpoint then restores the averages
     net.load_checkpoint(ckpt)
+    if a.ema and not net.ema_from_checkpoint:
+        raise SystemExit("%s carries no averaged weights: train with tools/train.py --ema_decay" % ckpt)
     trainer = NT(net, ds, denoise_train=a.denoise_train, seed=run_seed, degradation=degradation(a))
     row = {"iteration": int(state.get("iteration", net.iteration))}
     if a.latent_information + a.sample_quality + a.spectrum > 1:
@@ -129,7 +136,7 @@ def main(argv=None):
         report, name = trainer.sample_quality, "sample_quality.json"
     if a.spectrum:
         report, name = trainer.spectrum, "spectrum.json"
-    row.update(report(split=a.split, num_batches=a.num_batches, seed=a.seed))
+    row.update(report(split=a.split, num_batches=a.num_batches, seed=a.seed, weights="ema" if a.ema else "train"))
     line = json.dumps(row)
     with open(os.path.join(base_dir, name), "w") as f:
         f.write(line + "\n")

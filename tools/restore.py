@@ -32,6 +32,8 @@ def parse(argv=None):
     ap.add_argument("--known", default=None, help=".npy mask of the pixels to give back as they are")
     ap.add_argument("--range", default=None, metavar="LO,HI", help="the data range (default: the preset's)")
     ap.add_argument("--batch_size", type=int, default=None, help="default: the preset's")
+    ap.add_argument("--ema", action="store_true",
+                    help="restore with the Polyak-averaged weights the run kept (tools/train.py --ema_decay)")
     ap.add_argument("--dtype", default="bf16x6", choices=["fp32", "bf16", "bf16x6"])
     ap.add_argument("--models_dir", default="models")
     return ap.parse_args(argv)
@@ -66,14 +68,19 @@ def main(argv=None):
             state = json.load(f)
     net = SV(cfg, seed=int(state.get("seed", 0)))
     net.name = a.netname
+    if a.ema:
+        net.enable_ema()  # before loading: load_checkpoint then restores the averages
     net.load_checkpoint(ckpt)
+    if a.ema and not net.ema_from_checkpoint:
+        raise SystemExit("%s carries no averaged weights: train with tools/train.py --ema_decay" % ckpt)
     rng = tuple(float(v) for v in a.range.split(",")) if a.range else tuple(cfg.range)
     if len(rng) != 2:
         print("--range takes LO,HI")
         return 1
     steps = "all" if a.steps == "all" else int(a.steps)
     known = np.load(a.known) if a.known else None
-    out = net.restore(np.load(a.input), range=rng, stride=a.stride, steps=steps, seed=a.seed, known=known)
+    out = net.restore(np.load(a.input), range=rng, stride=a.stride, steps=steps, seed=a.seed, known=known,
+                      weights="ema" if a.ema else "train")
     np.save(a.output, out.cpu().numpy())
     print("%s: %s %s" % (a.output, tuple(out.shape), str(out.dtype).replace("torch.", "")))
     return 0

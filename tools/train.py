@@ -52,6 +52,13 @@ def parse(argv=None):
                     help="append NoisyTrainer.spectrum() of the test split (per-step radially averaged power spectra "
                          "of the outputs, their error and the generated samples against the clean images' own) to "
                          "<model dir>/spectrum.jsonl every N iterations (0: off)")
+    ap.add_argument("--ema_decay", type=float, default=None, metavar="D",
+                    help="keep Polyak averages of the weights with this decay (SequentialVAE.enable_ema): the "
+                         "checkpoint carries them, the periodic reports score both weights, and tools/evaluate.py "
+                         "--ema and tools/restore.py --ema use them (default: off)")
+    ap.add_argument("--ema_every", type=int, default=1, metavar="K", help="average every K-th step (decay ** K)")
+    ap.add_argument("--no_ema_warmup", action="store_true",
+                    help="use --ema_decay from the first step on instead of min(D, (1 + n) / (10 + n))")
     ap.add_argument("--iters", type=int, default=None, help="iterations to run (default: the reference's 10^7)")
     ap.add_argument("--dtype", default="bf16x6", choices=["fp32", "bf16", "bf16x6"])
     importlib.import_module(PKG + ".degrade").add_flags(ap)
@@ -132,7 +139,8 @@ def main(argv=None):
                  plot_reconstruction=a.plot_reconstruction, base_dir=base_dir, logger=log, seed=a.seed,
                  summary_freq=a.summary_freq, eval_frequency=a.eval_frequency,
                  info_frequency=a.info_frequency, quality_frequency=a.quality_frequency,
-                 degradation=degradation(a), spectrum_frequency=a.spectrum_frequency)
+                 degradation=degradation(a), spectrum_frequency=a.spectrum_frequency, ema_decay=a.ema_decay,
+                 ema_warmup=not a.no_ema_warmup, ema_every=a.ema_every)
     if a.continue_training and os.path.exists(os.path.join(base_dir, "trainer.json")):
         trainer.load(base_dir)
         log.info("resumed at iteration %d" % trainer.iteration)
