@@ -4,27 +4,20 @@
 //
 // Random draws are counter-based (philox.h): flat output element e of the [n * per_image] batch belongs to
 // group g = e / 4, lane j = e % 4; the 64-bit counter offset + g fills c0 / c1, c3 = 0 and c2 selects the
-// stream (0 normals, 1 pepper word, 2 salt word).  Nothing depends on the launch geometry or on the path
+// stream (philox.h: normals, pepper word, salt word).  Nothing depends on the launch geometry or on the path
 // (vector / scalar) the alignment selects.
+// MakeBatchArgs and the pixel noise are corrupt.h's, the dequantisation pixel.h's; svae_op_make_batch ends the file.
 #include <cstdint>
 
 #include "common.h"
 #include "corrupt.h"
-#include "kernels.h"
-#include "philox.h"
+#include "opentry.h"
+#include "pixel.h"
 
 namespace {
 
 constexpr int MB_THREADS = 256;
 constexpr int MB_TILE = MB_THREADS * 16;  // elements of one uint8 tile: one 16-byte load per lane
-
-// lo + q * qscale with the product and the sum each rounded to fp32 (the *_rn intrinsics are plain operators
-// to the compiler, which would contract them into one fma: the pragma keeps the two roundings the contract states)
-__device__ __forceinline__ float mb_dequant(unsigned char q, const MakeBatchArgs& a) {
-#pragma clang fp contract(off)
-  const float p = (float)q * a.qscale;
-  return a.lo + p;
-}
 
 __device__ __forceinline__ long long mb_row(const MakeBatchArgs& a, long long b) {
   return a.idx ? (long long)a.idx[b] : a.start + b;
@@ -68,9 +61,8 @@ __global__ __launch_bounds__(MB_THREADS) void make_batch_u8v_kernel(MakeBatchArg
       const int q = k * MB_THREADS + threadIdx.x;
       const long long e = tile * MB_TILE + (long long)q * 4;
       if (e < a.total) {
-        const unsigned w = words[q];
-        const float t[4] = {mb_dequant((unsigned char)(w & 0xFF), a), mb_dequant((unsigned char)((w >> 8) & 0xFF), a),
-                            mb_dequant((unsigned char)((w >> 16) & 0xFF), a), mb_dequant((unsigned char)(w >> 24), a)};
+        float t[4];
+        u8_dequant4(words[q], a.lo, a.qscale, t);
         if (a.input) {
           float o[4];
           mb_corrupt(t, e >> 2, a, o);
@@ -96,7 +88,7 @@ __global__ __launch_bounds__(MB_THREADS) void make_batch_scalar_kernel(MakeBatch
     for (int j = 0; j < 4; ++j) {
       if (e + j < a.total) {
         const long long src = mb_row(a, b) * a.per_image + off;
-        t[j] = U8 ? mb_dequant(((const unsigned char*)a.data)[src], a) : ((const float*)a.data)[src];
+        t[j] = U8 ? u8_dequant(((const unsigned char*)a.data)[src], a.lo, a.qscale) : ((const float*)a.data)[src];
       }
       if (++off == a.per_image) { off = 0; ++b; }
     }
@@ -110,10 +102,6 @@ __global__ __launch_bounds__(MB_THREADS) void make_batch_scalar_kernel(MakeBatch
       }
   }
 }
-
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-}  // namespace
 
 void make_batch(const MakeBatchArgs& a, hipStream_t s) {
   const bool al = al16(a.data) && al16(a.target) && al16(a.input);
@@ -132,3 +120,37 @@ void make_batch(const MakeBatchArgs& a, hipStream_t s) {
   else
     hipLaunchKernelGGL(make_batch_scalar_kernel<false>, grid, dim3(MB_THREADS), 0, s, a);
 }
+
+}  // namespace
+
+extern "C" {
+
+int svae_op_make_batch(const void* data, int data_u8, const int32_t* idx, int64_t start, int n, int64_t per_image,
+                       float lo, float hi, float pepper_prob, float salt_prob, float gaussian_scale, uint64_t seed,
+                       uint64_t offset, float* target, float* input, void* stream) {
+  if (!data) return op_fail(SVAE_EBADARG, "make_batch: null data");
+  if (!target && !input) return op_fail(SVAE_EBADARG, "make_batch: target and input are both null");
+  if (n <= 0 || per_image <= 0) return op_fail(SVAE_EBADARG, "make_batch: n and per_image must be positive");
+  if (!(pepper_prob >= 0.f && pepper_prob <= 1.f) || !(salt_prob >= 0.f && salt_prob <= 1.f))
+    return op_fail(SVAE_EBADARG, "make_batch: a probability outside [0, 1]");
+  if (!(gaussian_scale >= 0.f)) return op_fail(SVAE_EBADARG, "make_batch: negative gaussian_scale");
+  if (!(lo <= hi)) return op_fail(SVAE_EBADARG, "make_batch: lo > hi");
+  if (!idx && start < 0) return op_fail(SVAE_EBADARG, "make_batch: negative start");
+  // in place: every lane overwrites exactly what it read, which holds only for the identity gather of fp32 rows
+  if (((const void*)input == data || (const void*)target == data) && (data_u8 || idx || start != 0))
+    return op_fail(SVAE_EBADARG, "make_batch: in place needs fp32 data, idx == NULL and start == 0");
+  MakeBatchArgs a{};
+  a.data = data; a.data_u8 = data_u8 ? 1 : 0;
+  a.idx = idx; a.start = start;
+  a.per_image = per_image; a.total = (long long)n * per_image;
+  a.lo = lo; a.hi = hi;
+  a.qscale = quant_scale(lo, hi).qscale;
+  a.scale = gaussian_scale;
+  a.thr_pepper = prob_threshold(pepper_prob); a.thr_salt = prob_threshold(salt_prob);
+  a.seed = seed; a.offset = offset;
+  a.target = target; a.input = input;
+  make_batch(a, (hipStream_t)stream);
+  return op_done();
+}
+
+}  // extern "C"

@@ -2,10 +2,9 @@
 // include/svae_hip.h): per row an image, an integer box scale, one of up to eight symmetries and a window origin,
 // then the means of the s x s source blocks of that window, mirrored / transposed, dequantised.
 //
-// Per-row draws are Philox4x32-10 under the key (lo32(seed), hi32(seed)) with the counter words (offset + b in
-// c0 / c1, c2 = 4, c3 = block): stream 4 is one neither make_batch (0 .. 2) nor degrade_batch (3) uses.  Block 0
-// gives image, scale and symmetry, block 1 the origin; a block whose words cannot matter (every range is 1) is not
-// drawn.  Sums are exact integers (uint8) or fp32 in a fixed order (fp32), every fp32 operation is rounded on its
+// Per-row draws are philox.h's philox_image on the stream PHILOX_CROPS: block 0 gives image, scale and symmetry,
+// block 1 the origin; a block whose words cannot matter (every range is 1) is not drawn.  The dequantisation is
+// pixel.h's.  Sums are exact integers (uint8) or fp32 in a fixed order (fp32), every fp32 operation is rounded on its
 // own (contract(off)), so the result depends on the arguments alone: not on the launch, not on whether a block
 // staged its source patch in LDS or read it from global memory, not on the path (16-byte / element) the alignment
 // of a source row selects.
@@ -22,25 +21,36 @@
 // A block whose patch does not fit what the launch reserved (no LDS at all when the largest scale's patch exceeds
 // 64 KB less the header at T = 16; a scale beyond the listed ones in explicit crops) reduces from global memory
 // instead: the same values enter the same operations in the same order.
+// svae_op_crop_batch, with its argument checks, ends the file.
+#include <algorithm>
 #include <cstdint>
 
 #include "common.h"
-#include "kernels.h"
+#include "opentry.h"
 #include "philox.h"
+#include "pixel.h"
 
 namespace {
+
+// row b of the batch = the h x w window at (y0, x0) of image m, box-averaged by s and mapped by symmetry g, with
+// (m, s, g, y0, x0) = crops[b], or drawn when crops == nullptr
+struct CropArgs {
+  const void* images; int data_u8;
+  int nimg, H, W, c, h, w;
+  int n_scales, scales[4], smax;     // smax: the largest listed scale (what the LDS patch is sized for)
+  int symmetries;
+  const int* crops;
+  unsigned long long seed, offset;
+  int n;
+  float lo, qscale;                  // qscale = (hi - lo) / 255 rounded to fp32 (make_batch's)
+  float* target; unsigned char* target_u8; int* meta;   // target or target_u8 may be nullptr, meta may be
+};
 
 constexpr int CR_THREADS = 256;
 constexpr int CR_HDR = 32;                 // bytes ahead of the patch: the row's five parameters
 constexpr long long CR_LDS_MAX = 65536 - CR_HDR;  // the patch of a 16 x 16 tile must fit this, or nothing is staged
 constexpr long long CR_LDS_WIDE = 32768;   // a 32 x 32 tile is used while its patch fits this (four blocks a CU)
 constexpr long long CR_GRID_CAP = 1 << 20;  // grid-stride beyond this many blocks
-
-__device__ __forceinline__ void cr_words(const CropArgs& a, long long b, unsigned blk, unsigned w[4]) {
-  const unsigned long long ctr = a.offset + (unsigned long long)b;
-  w[0] = (unsigned)ctr; w[1] = (unsigned)(ctr >> 32); w[2] = 4; w[3] = blk;
-  philox(w[0], w[1], w[2], w[3], (unsigned)a.seed, (unsigned)(a.seed >> 32));
-}
 
 // (m, s, g, y0, x0) of row b: crops[b] as it is, or the draws
 __device__ __forceinline__ void cr_params(const CropArgs& a, long long b, int p[5]) {
@@ -52,7 +62,7 @@ __device__ __forceinline__ void cr_params(const CropArgs& a, long long b, int p[
   unsigned w[4];
   p[0] = 0; p[1] = a.scales[0]; p[2] = 0; p[3] = 0; p[4] = 0;
   if (a.nimg > 1 || a.n_scales > 1 || a.symmetries > 1) {
-    cr_words(a, b, 0, w);
+    philox_image(a.seed, a.offset, b, PHILOX_CROPS, 0, w);
     p[0] = (int)__umulhi(w[0], (unsigned)a.nimg);
     const int k = (int)__umulhi(w[1], (unsigned)a.n_scales);
     p[1] = k == 0 ? a.scales[0] : (k == 1 ? a.scales[1] : (k == 2 ? a.scales[2] : a.scales[3]));
@@ -60,7 +70,7 @@ __device__ __forceinline__ void cr_params(const CropArgs& a, long long b, int p[
   }
   const unsigned ny = (unsigned)(a.H - p[1] * a.h + 1), nx = (unsigned)(a.W - p[1] * a.w + 1);
   if (ny > 1 || nx > 1) {
-    cr_words(a, b, 1, w);
+    philox_image(a.seed, a.offset, b, PHILOX_CROPS, 1, w);
     p[3] = (int)__umulhi(w[0], ny);
     p[4] = (int)__umulhi(w[1], nx);
   }
@@ -82,10 +92,7 @@ __device__ __forceinline__ void cr_pixel(const CropArgs& a, const unsigned char*
     }
     float mean = (float)sum;  // exact: at most 64 * 255
     if (s > 1) mean = __fdiv_rn(mean, (float)(s * s));
-    if (a.target) {
-      const float pr = mean * a.qscale;
-      a.target[o] = a.lo + pr;
-    }
+    if (a.target) a.target[o] = u8_dequant(mean, a.lo, a.qscale);
     if (a.target_u8) a.target_u8[o] = (unsigned char)fminf(255.f, rintf(mean));
   } else {
     const unsigned char* row = src + r0 * pitch + (LDS ? ((mis0 + r0 * rb16) & 15) : 0);
@@ -220,7 +227,42 @@ inline void cr_patch(const CropArgs& a, int T, int& rows, int& chunks) {
 
 }  // namespace
 
-void crop_batch(const CropArgs& a, hipStream_t s) {
+extern "C" {
+
+int svae_op_crop_batch(const void* images, int data_u8, int nimg, int H, int W, int c, int h, int w,
+                       const svae_crop_spec* spec, const int32_t* crops, uint64_t seed, uint64_t offset, int n,
+                       float lo, float hi, float* target, uint8_t* target_u8, int32_t* meta, void* stream) {
+  if (!images || !spec) return op_fail(SVAE_EBADARG, "crop_batch: null images or spec");
+  if (!target && !target_u8) return op_fail(SVAE_EBADARG, "crop_batch: target and target_u8 are both null");
+  if (target_u8 && !data_u8) return op_fail(SVAE_EBADARG, "crop_batch: target_u8 needs uint8 images");
+  if (nimg <= 0 || H <= 0 || W <= 0 || c <= 0 || h <= 0 || w <= 0 || n <= 0)
+    return op_fail(SVAE_EBADARG, "crop_batch: nimg, H, W, c, h, w and n must be positive");
+  const svae_crop_spec& p = *spec;
+  if (p.n_scales < 1 || p.n_scales > 4) return op_fail(SVAE_EBADARG, "crop_batch: n_scales must be in 1 .. 4");
+  int smax = 0;
+  for (int k = 0; k < p.n_scales; ++k) {
+    const int s = p.scales[k];
+    if (s < 1 || s > 8) return op_fail(SVAE_EBADARG, "crop_batch: a scale outside 1 .. 8");
+    for (int j = 0; j < k; ++j)
+      if (p.scales[j] == s) return op_fail(SVAE_EBADARG, "crop_batch: a scale is listed twice");
+    if ((int64_t)s * h > H || (int64_t)s * w > W)
+      return op_fail(SVAE_EBADARG, "crop_batch: a scaled tile exceeds the image");
+    smax = std::max(smax, s);
+  }
+  if (p.symmetries != 1 && p.symmetries != 2 && p.symmetries != 4 && p.symmetries != 8)
+    return op_fail(SVAE_EBADARG, "crop_batch: symmetries must be 1, 2, 4 or 8");
+  if (p.symmetries == 8 && h != w) return op_fail(SVAE_EBADARG, "crop_batch: the dihedral group needs h == w");
+  if (data_u8 && !(lo < hi)) return op_fail(SVAE_EBADARG, "crop_batch: lo >= hi with uint8 images");
+  if ((int64_t)H * W * c > 2147483647LL || (int64_t)h * w * c > 2147483647LL)
+    return op_fail(SVAE_EBADCONFIG, "crop_batch: at most 2^31 - 1 elements per image and per tile");
+  CropArgs a{};
+  a.images = images; a.data_u8 = data_u8 ? 1 : 0;
+  a.nimg = nimg; a.H = H; a.W = W; a.c = c; a.h = h; a.w = w;
+  a.n_scales = p.n_scales; a.smax = smax; a.symmetries = p.symmetries;
+  for (int k = 0; k < 4; ++k) a.scales[k] = k < p.n_scales ? p.scales[k] : p.scales[0];
+  a.crops = crops; a.seed = seed; a.offset = offset; a.n = n;
+  a.lo = lo; a.qscale = quant_scale(lo, hi).qscale;
+  a.target = target; a.target_u8 = target_u8; a.meta = meta;
   int tile = 16, rows = 0, chunks = 0;
   cr_patch(a, 32, rows, chunks);
   if ((long long)rows * chunks * 16 <= CR_LDS_WIDE) {
@@ -232,6 +274,10 @@ void crop_batch(const CropArgs& a, hipStream_t s) {
   const long long items = (long long)a.n * ((a.h + tile - 1) / tile) * ((a.w + tile - 1) / tile);
   const dim3 grid((unsigned)(items < CR_GRID_CAP ? items : CR_GRID_CAP)), block(CR_THREADS);
   const size_t lds = (size_t)CR_HDR + (size_t)rows * chunks * 16;
+  hipStream_t s = (hipStream_t)stream;
   if (a.data_u8) hipLaunchKernelGGL(crop_batch_kernel<true>, grid, block, lds, s, a, tile, rows, chunks);
   else hipLaunchKernelGGL(crop_batch_kernel<false>, grid, block, lds, s, a, tile, rows, chunks);
+  return op_done();
 }
+
+}  // extern "C"

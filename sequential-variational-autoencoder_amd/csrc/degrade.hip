@@ -2,8 +2,7 @@
 // Gaussian blur, a box down-sampling replicated back to full size and cut-out boxes, then svae_op_make_batch's
 // pixel noise and clip (corrupt.h: the one copy of it).
 //
-// Per-image draws are Philox4x32-10 under the key (lo32(seed), hi32(seed)) with the counter words (offset + b in
-// c0 / c1, c2 = 3, c3 = block): stream 3 is the one make_batch leaves unused.  Block 0 gives the three gates and
+// Per-image draws are philox.h's philox_image on the stream PHILOX_DEGRADE: block 0 gives the three gates and
 // sigma, block 1 + k the integer geometry of box k.  Every sum has a fixed order and every operation is rounded
 // on its own (contract(off)), so the result depends on the arguments alone: not on the launch, not on whether
 // the band kernel or the global-memory kernel ran, not on the path (16-byte / scalar) the alignment selects.
@@ -12,14 +11,25 @@
 // blocks).  It stages the band and r halo rows above and below into LDS (edge rows replicated), blurs horizontally
 // LDS -> LDS over all staged rows, vertically over the band's rows, averages the down-sample blocks through LDS and
 // walks the band's share of the flat batch in groups of four for the cut-out, the pixel noise and the store.
+// svae_op_degrade_batch, with its argument checks and the bound rmax the LDS band is sized for, ends the file.
 #include <cstdint>
 
 #include "common.h"
 #include "corrupt.h"
-#include "kernels.h"
-#include "philox.h"
+#include "opentry.h"
 
 namespace {
+
+// target [n,h,w,c] -> input (and mask [n,h,w], may be nullptr); nz carries the pixel noise (what mb_corrupt reads)
+struct DegradeArgs {
+  const float* target; float* input; float* mask;
+  int n, h, w, c;
+  unsigned thr_blur, thr_down, thr_cut;
+  float sigma_lo, sigma_hi, fill;
+  int factor, boxes, min_side, max_side;
+  int rmax;                          // min(ceil(3 sigma_hi), 12), 0 without blur: what the LDS band is sized for
+  MakeBatchArgs nz;
+};
 
 constexpr int DG_THREADS = 512;  // band kernel: 8 waves a block, two blocks a CU at CelebA geometry (LDS bound)
 constexpr int DG_RMAX = 12;  // taps reach min(ceil(3 sigma), 12) pixels
@@ -31,17 +41,11 @@ struct DgDraws {
   float sigma;
 };
 
-__device__ __forceinline__ void dg_words(const DegradeArgs& a, long long b, unsigned blk, unsigned w[4]) {
-  const unsigned long long ctr = a.nz.offset + (unsigned long long)b;
-  w[0] = (unsigned)ctr; w[1] = (unsigned)(ctr >> 32); w[2] = 3; w[3] = blk;
-  philox(w[0], w[1], w[2], w[3], (unsigned)a.nz.seed, (unsigned)(a.nz.seed >> 32));
-}
-
 // block 0: the gates, sigma and the tap radius
 __device__ __forceinline__ DgDraws dg_draws(const DegradeArgs& a, long long b) {
 #pragma clang fp contract(off)
   unsigned w[4];
-  dg_words(a, b, 0, w);
+  philox_image(a.nz.seed, a.nz.offset, b, PHILOX_DEGRADE, 0, w);
   DgDraws d;
   const float u = (float)(w[1] >> 8) * 5.9604644775390625e-8f;  // 2^-24: exact
   const float span = a.sigma_hi - a.sigma_lo;
@@ -60,7 +64,7 @@ __device__ __forceinline__ DgDraws dg_draws(const DegradeArgs& a, long long b) {
 // block 1 + k: box k as (y0, x0, height, width), all integer
 __device__ __forceinline__ void dg_box(const DegradeArgs& a, long long b, int k, int box[4]) {
   unsigned w[4];
-  dg_words(a, b, 1u + (unsigned)k, w);
+  philox_image(a.nz.seed, a.nz.offset, b, PHILOX_DEGRADE, 1u + (unsigned)k, w);
   const unsigned span = (unsigned)(a.max_side - a.min_side) + 1u;
   const int bh = min(a.h, a.min_side + (int)__umulhi(w[0], span));
   const int bw = min(a.w, a.min_side + (int)__umulhi(w[1], span));
@@ -355,10 +359,7 @@ __global__ __launch_bounds__(DG_THREADS) void degrade_global_kernel(DegradeArgs 
   }
 }
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-}  // namespace
-
+// bytes of LDS the band kernel needs for bands of `band` rows (degrade_batch falls back to global memory above 64 KB)
 long long degrade_lds_bytes(const DegradeArgs& a, int band) {
   const long long rows = (long long)(band < a.h ? band : a.h) + 2 * a.rmax;
   return 4 * (DG_HDR + 2 * rows * a.w * a.c);
@@ -381,3 +382,47 @@ void degrade_batch(const DegradeArgs& a, hipStream_t s) {
   const long long cap = 16384;  // grid-stride beyond this many blocks
   hipLaunchKernelGGL(degrade_global_kernel, dim3((unsigned)(nb < cap ? nb : cap)), dim3(DG_THREADS), 0, s, a);
 }
+
+}  // namespace
+
+extern "C" {
+
+int svae_op_degrade_batch(const float* target, int n, int h, int w, int c, float lo, float hi,
+                          const svae_degrade_spec* spec, uint64_t seed, uint64_t offset, float* input, float* mask,
+                          void* stream) {
+  if (!target || !input || !spec) return op_fail(SVAE_EBADARG, "degrade_batch: null target, input or spec");
+  if (input == target) return op_fail(SVAE_EBADARG, "degrade_batch: in place is not possible (the blur reads neighbours)");
+  if (n <= 0 || h <= 0 || w <= 0 || c <= 0) return op_fail(SVAE_EBADARG, "degrade_batch: n, h, w and c must be positive");
+  const int64_t per_image = (int64_t)h * w * c;
+  if (per_image < 4) return op_fail(SVAE_EBADARG, "degrade_batch: h * w * c must be at least 4");
+  if (per_image > 2147483647LL) return op_fail(SVAE_EBADCONFIG, "degrade_batch: at most 2^31 - 1 elements per image");
+  const svae_degrade_spec& p = *spec;
+  auto prob = [](float v) { return v >= 0.f && v <= 1.f; };
+  if (!prob(p.p_blur) || !prob(p.p_down) || !prob(p.p_cut) || !prob(p.pepper_prob) || !prob(p.salt_prob))
+    return op_fail(SVAE_EBADARG, "degrade_batch: a probability outside [0, 1]");
+  if (!(p.sigma_lo >= 0.f) || !(p.sigma_lo <= p.sigma_hi) || !(p.sigma_hi <= 4.f))
+    return op_fail(SVAE_EBADARG, "degrade_batch: need 0 <= sigma_lo <= sigma_hi <= 4");
+  if (p.factor != 1 && p.factor != 2 && p.factor != 4 && p.factor != 8)
+    return op_fail(SVAE_EBADARG, "degrade_batch: factor must be 1, 2, 4 or 8");
+  if (p.boxes < 0 || p.boxes > 4) return op_fail(SVAE_EBADARG, "degrade_batch: boxes must be in 0 .. 4");
+  if (p.min_side < 1 || p.min_side > p.max_side)
+    return op_fail(SVAE_EBADARG, "degrade_batch: need 1 <= min_side <= max_side");
+  if (!(p.gaussian_scale >= 0.f)) return op_fail(SVAE_EBADARG, "degrade_batch: negative gaussian_scale");
+  if (!(lo <= hi)) return op_fail(SVAE_EBADARG, "degrade_batch: lo > hi");
+  DegradeArgs a{};
+  a.target = target; a.input = input; a.mask = mask;
+  a.n = n; a.h = h; a.w = w; a.c = c;
+  a.thr_blur = prob_threshold(p.p_blur); a.thr_down = prob_threshold(p.p_down); a.thr_cut = prob_threshold(p.p_cut);
+  a.sigma_lo = p.sigma_lo; a.sigma_hi = p.sigma_hi; a.fill = p.fill;
+  a.factor = p.factor; a.boxes = p.boxes; a.min_side = p.min_side; a.max_side = p.max_side;
+  // the largest tap radius a draw can give: sigma <= sigma_hi, and the kernel forms ceilf(3.f * sigma) alike
+  const int rmax = (int)std::ceil(3.f * p.sigma_hi);
+  a.rmax = a.thr_blur ? (rmax < 12 ? rmax : 12) : 0;
+  a.nz.lo = lo; a.nz.hi = hi; a.nz.scale = p.gaussian_scale;
+  a.nz.thr_pepper = prob_threshold(p.pepper_prob); a.nz.thr_salt = prob_threshold(p.salt_prob);
+  a.nz.seed = seed; a.nz.offset = offset;
+  degrade_batch(a, (hipStream_t)stream);
+  return op_done();
+}
+
+}  // extern "C"

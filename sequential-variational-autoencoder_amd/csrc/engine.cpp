@@ -20,6 +20,7 @@
 
 #include "kernels.h"
 #include "knobs.h"
+#include "opentry.h"
 #include "svae_hip.h"
 
 namespace {
@@ -493,7 +494,7 @@ thread_local std::string g_tls_err;
 
 }  // namespace
 
-// the context-free ops of other translation units (pcnn.hip) report through svae_last_error(NULL)
+// the context-free ops of other translation units (opentry.h, pcnn.hip) report through svae_last_error(NULL)
 void svae_tls_error(const std::string& msg) { g_tls_err = msg; }
 
 // ============================================================================
@@ -3378,16 +3379,6 @@ int svae_copy_out(svae_ctx* c, int which, int step, float* dst, int64_t n, void*
   return 0;
 }
 
-int svae_op_ema(float* ema, const float* w, int64_t n, float omd, void* stream) {
-  if (!ema || !w) return fail(nullptr, SVAE_EBADARG, "ema: null pointer");
-  if (n <= 0) return fail(nullptr, SVAE_EBADARG, "ema: n must be positive");
-  if (!(omd >= 0.f && omd <= 1.f)) return fail(nullptr, SVAE_EBADARG, "ema: omd must be in [0, 1]");
-  if (omd == 0.f) return 0;
-  ema_update(ema, w, n, omd, (hipStream_t)stream);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
-}
-
 }  // extern "C"
 
 // ============================================================================
@@ -3405,8 +3396,7 @@ int svae_op_conv(const float* x, int n, int h, int cin, const float* w, int cout
   a.A = x; a.lda = cin;
   a.C = y; a.ldc = cout;
   igemm_fwd(a, 1, (hipStream_t)stream);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
+  return op_done();
 }
 
 int svae_op_gather_bf16(const float* x, int n, int h, int cin, const void* w_nk, int cout, int stride, int transpose,
@@ -3432,8 +3422,7 @@ int svae_op_gather_bf16(const float* x, int n, int h, int cin, const void* w_nk,
   }
   if (igemm_bf16_path(a, 1, path, (hipStream_t)stream) < 0)
     return fail(nullptr, SVAE_EBADARG, "shape does not qualify for the halo-tile kernel");
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
+  return op_done();
 }
 
 // the context svae_op_wgrad_bf16 runs conv_wgrad on (process-wide: a test entry point, one caller at a time)
@@ -3468,8 +3457,7 @@ int svae_op_wgrad_bf16(const float* x, int n, int h, int cin, const float* dy, i
   dummy.m.g.split = 0;
   dummy.dbf = 0;
   if (r) return fail(nullptr, r, dummy.err);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
+  return op_done();
 }
 
 int svae_op_wgrad_last_kernel(void) { return wgrad_op_ctx().wg_last; }
@@ -3487,8 +3475,7 @@ int svae_op_conv_dgrad(const float* dy, int n, int h, int cin, const float* w, i
   L.ow = 0;
   int r = conv_dgrad(&dummy, L, 1, 0, dy, 0, View{dx, cin, 0}, 0);
   if (r) return fail(nullptr, r, dummy.err);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
+  return op_done();
 }
 
 int svae_op_conv_wgrad(const float* x, int n, int h, int cin, const float* dy, int cout, int stride, int transpose,
@@ -3504,8 +3491,7 @@ int svae_op_conv_wgrad(const float* x, int n, int h, int cin, const float* dy, i
   L.hout = L.tr ? h * stride : h / stride;
   int r = conv_wgrad(&dummy, L, 1, 0, View{(float*)x, cin, 0}, dy, 0, dw);
   if (r) return fail(nullptr, r, dummy.err);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
+  return op_done();
 }
 
 int svae_op_bn_act(const float* x, int64_t rows, int c, const float* beta, int act, float* y, float* mean,
@@ -3523,8 +3509,7 @@ int svae_op_bn_act(const float* x, int64_t rows, int c, const float* beta, int a
   // sum(x), sum(x^2) via the backward reducer with act=none, mean=0, invstd=1
   bn_bwd_reduce(x, c, 0, x, c, 0, x, c, 0, rows, c, zi, zi + c, 0, nullptr, 0, ACT_NONE, acc, 0, 4LL * c, nsh, 1, s);
   bn_apply(x, c, 0, rows, c, acc, 0, 4LL * c, nsh, 1e-3f, mean, invstd, 0, beta, 0, nullptr, 0, 0, act, y, c, 0, 1, s);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
+  return op_done();
 }
 
 int svae_op_bn_act_bwd(const float* dy, const float* y, const float* x, int64_t rows, int c, const float* mean,
@@ -3543,8 +3528,7 @@ int svae_op_bn_act_bwd(const float* dy, const float* y, const float* x, int64_t 
   int r = bn_act_bwd(&dummy, 1, rows, c, View{(float*)dy, c, 0}, View{(float*)y, c, 0}, x, 0, c, bn, 0, 0, 0, act, dx,
                      0, View{}, 0);
   if (r) return fail(nullptr, r, dummy.err);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
+  return op_done();
 }
 
 int svae_op_flat_conv(const float* x, int n, int h, int cin, const float* w, int cout, const float* in_mean,
@@ -3567,8 +3551,7 @@ int svae_op_flat_conv(const float* x, int n, int h, int cin, const float* w, int
   if (in_mean) { in.mode = 1; in.mean = in_mean; in.invstd = in_invstd; in.beta = in_beta; }
   flat_conv(in, n, h, cin, w, cout, 0, nullptr, y, cout, FlatOut{}, stats_out ? part : nullptr, s);
   if (stats_out) sd_stat_fin(part, flat_blocks(n, h), cout, 1, 0.f, 1, nullptr, nullptr, stats_out, nullptr, s);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
+  return op_done();
 }
 
 int svae_op_flat_dgrad(const float* dy, int n, int h, int cin, const float* w, int cout, float* dx, void* stream) {
@@ -3577,8 +3560,7 @@ int svae_op_flat_dgrad(const float* dy, int n, int h, int cin, const float* w, i
   FlatIn in;
   in.p = dy;
   flat_conv(in, n, h, cout, w, cin, 1, nullptr, dx, cin, FlatOut{}, nullptr, (hipStream_t)stream);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
+  return op_done();
 }
 
 int svae_op_flat_wgrad(const float* x, int n, int h, int cin, const float* dy, int cout, float* dw, void* scratch,
@@ -3591,8 +3573,7 @@ int svae_op_flat_wgrad(const float* x, int n, int h, int cin, const float* dy, i
   in.p = x;
   d.p = dy;
   flat_wgrad(in, d, n, h, cin, cout, (float*)scratch, dw, (hipStream_t)stream);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
+  return op_done();
 }
 
 int svae_op_fc(const float* x, int b, int k, const float* w, int nout, float* y, void* stream) {
@@ -3605,8 +3586,7 @@ int svae_op_fc(const float* x, int b, int k, const float* w, int nout, float* y,
   a.g.mode = GM_DENSE; a.g.nimg = b; a.g.ksz = 1; a.g.stride = 1;
   a.rows = b; a.nclass = 1;
   igemm_fwd(a, 1, (hipStream_t)stream);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
+  return op_done();
 }
 
 // ---- recognition heads, latent and split-latent (misc.hip): the engine's launchers with its own strides ----
@@ -3614,11 +3594,6 @@ static_assert(SVAE_HEADS_FWD_NARROW == HEADS_FWD_NARROW && SVAE_HEADS_FWD_TILE =
               SVAE_HEADS_FWD_SKINNY == HEADS_FWD_SKINNY && SVAE_HEADS_BWD_ROWGROUP == HEADS_BWD_ROWGROUP &&
               SVAE_HEADS_BWD_PLAIN == HEADS_BWD_PLAIN && SVAE_HEADS_BWD_TILE == HEADS_BWD_TILE,
               "include/svae_hip.h and kernels.h name the heads kernels alike");
-
-static int op_done() {
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
-}
 
 int svae_op_dense_bf16(const void* x, int b, int k, const void* w_nk, int nout, int path, float* y, void* scratch,
                        int64_t scratch_bytes, int32_t* variant, void* stream) {
@@ -3778,376 +3753,6 @@ int svae_op_splitfc_bwd(const float* z, int ldz, int zoff, int b, int k, const f
   splitfc_bwd(z, ldz, zoff, b, k, w, beta, j, mean, invstd, dout, o_n, f, ldo, dw, dbeta, (float*)scratch, s);
   splitfc_dz_reduce((const float*)scratch, splitfc_blocks(j), b, k, dz, ldz, zoff, s);
   return op_done();
-}
-
-// thr(p) = min(floor(p 2^32), 2^32 - 1): a word w < thr(p) with probability p
-static uint32_t prob_threshold(float p) {
-  const double t = std::floor((double)p * 4294967296.0);
-  return t >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)t;
-}
-
-int svae_op_make_batch(const void* data, int data_u8, const int32_t* idx, int64_t start, int n, int64_t per_image,
-                       float lo, float hi, float pepper_prob, float salt_prob, float gaussian_scale, uint64_t seed,
-                       uint64_t offset, float* target, float* input, void* stream) {
-  if (!data) return fail(nullptr, SVAE_EBADARG, "make_batch: null data");
-  if (!target && !input) return fail(nullptr, SVAE_EBADARG, "make_batch: target and input are both null");
-  if (n <= 0 || per_image <= 0) return fail(nullptr, SVAE_EBADARG, "make_batch: n and per_image must be positive");
-  if (!(pepper_prob >= 0.f && pepper_prob <= 1.f) || !(salt_prob >= 0.f && salt_prob <= 1.f))
-    return fail(nullptr, SVAE_EBADARG, "make_batch: a probability outside [0, 1]");
-  if (!(gaussian_scale >= 0.f)) return fail(nullptr, SVAE_EBADARG, "make_batch: negative gaussian_scale");
-  if (!(lo <= hi)) return fail(nullptr, SVAE_EBADARG, "make_batch: lo > hi");
-  if (!idx && start < 0) return fail(nullptr, SVAE_EBADARG, "make_batch: negative start");
-  // in place: every lane overwrites exactly what it read, which holds only for the identity gather of fp32 rows
-  if (((const void*)input == data || (const void*)target == data) && (data_u8 || idx || start != 0))
-    return fail(nullptr, SVAE_EBADARG, "make_batch: in place needs fp32 data, idx == NULL and start == 0");
-  MakeBatchArgs a{};
-  a.data = data; a.data_u8 = data_u8 ? 1 : 0;
-  a.idx = idx; a.start = start;
-  a.per_image = per_image; a.total = (long long)n * per_image;
-  a.lo = lo; a.hi = hi;
-  a.qscale = (float)(((double)hi - (double)lo) / 255.0);
-  a.scale = gaussian_scale;
-  a.thr_pepper = prob_threshold(pepper_prob); a.thr_salt = prob_threshold(salt_prob);
-  a.seed = seed; a.offset = offset;
-  a.target = target; a.input = input;
-  make_batch(a, (hipStream_t)stream);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
-}
-
-int svae_op_degrade_batch(const float* target, int n, int h, int w, int c, float lo, float hi,
-                          const svae_degrade_spec* spec, uint64_t seed, uint64_t offset, float* input, float* mask,
-                          void* stream) {
-  if (!target || !input || !spec) return fail(nullptr, SVAE_EBADARG, "degrade_batch: null target, input or spec");
-  if (input == target) return fail(nullptr, SVAE_EBADARG, "degrade_batch: in place is not possible (the blur reads neighbours)");
-  if (n <= 0 || h <= 0 || w <= 0 || c <= 0) return fail(nullptr, SVAE_EBADARG, "degrade_batch: n, h, w and c must be positive");
-  const int64_t per_image = (int64_t)h * w * c;
-  if (per_image < 4) return fail(nullptr, SVAE_EBADARG, "degrade_batch: h * w * c must be at least 4");
-  if (per_image > 2147483647LL) return fail(nullptr, SVAE_EBADCONFIG, "degrade_batch: at most 2^31 - 1 elements per image");
-  const svae_degrade_spec& p = *spec;
-  auto prob = [](float v) { return v >= 0.f && v <= 1.f; };
-  if (!prob(p.p_blur) || !prob(p.p_down) || !prob(p.p_cut) || !prob(p.pepper_prob) || !prob(p.salt_prob))
-    return fail(nullptr, SVAE_EBADARG, "degrade_batch: a probability outside [0, 1]");
-  if (!(p.sigma_lo >= 0.f) || !(p.sigma_lo <= p.sigma_hi) || !(p.sigma_hi <= 4.f))
-    return fail(nullptr, SVAE_EBADARG, "degrade_batch: need 0 <= sigma_lo <= sigma_hi <= 4");
-  if (p.factor != 1 && p.factor != 2 && p.factor != 4 && p.factor != 8)
-    return fail(nullptr, SVAE_EBADARG, "degrade_batch: factor must be 1, 2, 4 or 8");
-  if (p.boxes < 0 || p.boxes > 4) return fail(nullptr, SVAE_EBADARG, "degrade_batch: boxes must be in 0 .. 4");
-  if (p.min_side < 1 || p.min_side > p.max_side)
-    return fail(nullptr, SVAE_EBADARG, "degrade_batch: need 1 <= min_side <= max_side");
-  if (!(p.gaussian_scale >= 0.f)) return fail(nullptr, SVAE_EBADARG, "degrade_batch: negative gaussian_scale");
-  if (!(lo <= hi)) return fail(nullptr, SVAE_EBADARG, "degrade_batch: lo > hi");
-  DegradeArgs a{};
-  a.target = target; a.input = input; a.mask = mask;
-  a.n = n; a.h = h; a.w = w; a.c = c;
-  a.thr_blur = prob_threshold(p.p_blur); a.thr_down = prob_threshold(p.p_down); a.thr_cut = prob_threshold(p.p_cut);
-  a.sigma_lo = p.sigma_lo; a.sigma_hi = p.sigma_hi; a.fill = p.fill;
-  a.factor = p.factor; a.boxes = p.boxes; a.min_side = p.min_side; a.max_side = p.max_side;
-  // the largest tap radius a draw can give: sigma <= sigma_hi, and the kernel forms ceilf(3.f * sigma) alike
-  const int rmax = (int)std::ceil(3.f * p.sigma_hi);
-  a.rmax = a.thr_blur ? (rmax < 12 ? rmax : 12) : 0;
-  a.nz.lo = lo; a.nz.hi = hi; a.nz.scale = p.gaussian_scale;
-  a.nz.thr_pepper = prob_threshold(p.pepper_prob); a.nz.thr_salt = prob_threshold(p.salt_prob);
-  a.nz.seed = seed; a.nz.offset = offset;
-  degrade_batch(a, (hipStream_t)stream);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
-}
-
-int svae_op_crop_batch(const void* images, int data_u8, int nimg, int H, int W, int c, int h, int w,
-                       const svae_crop_spec* spec, const int32_t* crops, uint64_t seed, uint64_t offset, int n,
-                       float lo, float hi, float* target, uint8_t* target_u8, int32_t* meta, void* stream) {
-  if (!images || !spec) return fail(nullptr, SVAE_EBADARG, "crop_batch: null images or spec");
-  if (!target && !target_u8) return fail(nullptr, SVAE_EBADARG, "crop_batch: target and target_u8 are both null");
-  if (target_u8 && !data_u8) return fail(nullptr, SVAE_EBADARG, "crop_batch: target_u8 needs uint8 images");
-  if (nimg <= 0 || H <= 0 || W <= 0 || c <= 0 || h <= 0 || w <= 0 || n <= 0)
-    return fail(nullptr, SVAE_EBADARG, "crop_batch: nimg, H, W, c, h, w and n must be positive");
-  const svae_crop_spec& p = *spec;
-  if (p.n_scales < 1 || p.n_scales > 4) return fail(nullptr, SVAE_EBADARG, "crop_batch: n_scales must be in 1 .. 4");
-  int smax = 0;
-  for (int k = 0; k < p.n_scales; ++k) {
-    const int s = p.scales[k];
-    if (s < 1 || s > 8) return fail(nullptr, SVAE_EBADARG, "crop_batch: a scale outside 1 .. 8");
-    for (int j = 0; j < k; ++j)
-      if (p.scales[j] == s) return fail(nullptr, SVAE_EBADARG, "crop_batch: a scale is listed twice");
-    if ((int64_t)s * h > H || (int64_t)s * w > W)
-      return fail(nullptr, SVAE_EBADARG, "crop_batch: a scaled tile exceeds the image");
-    smax = std::max(smax, s);
-  }
-  if (p.symmetries != 1 && p.symmetries != 2 && p.symmetries != 4 && p.symmetries != 8)
-    return fail(nullptr, SVAE_EBADARG, "crop_batch: symmetries must be 1, 2, 4 or 8");
-  if (p.symmetries == 8 && h != w) return fail(nullptr, SVAE_EBADARG, "crop_batch: the dihedral group needs h == w");
-  if (data_u8 && !(lo < hi)) return fail(nullptr, SVAE_EBADARG, "crop_batch: lo >= hi with uint8 images");
-  if ((int64_t)H * W * c > 2147483647LL || (int64_t)h * w * c > 2147483647LL)
-    return fail(nullptr, SVAE_EBADCONFIG, "crop_batch: at most 2^31 - 1 elements per image and per tile");
-  CropArgs a{};
-  a.images = images; a.data_u8 = data_u8 ? 1 : 0;
-  a.nimg = nimg; a.H = H; a.W = W; a.c = c; a.h = h; a.w = w;
-  a.n_scales = p.n_scales; a.smax = smax; a.symmetries = p.symmetries;
-  for (int k = 0; k < 4; ++k) a.scales[k] = k < p.n_scales ? p.scales[k] : p.scales[0];
-  a.crops = crops; a.seed = seed; a.offset = offset; a.n = n;
-  a.lo = lo; a.qscale = (float)(((double)hi - (double)lo) / 255.0);
-  a.target = target; a.target_u8 = target_u8; a.meta = meta;
-  crop_batch(a, (hipStream_t)stream);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
-}
-
-int svae_op_jpeg_batch(const float* in, int n, int h, int w, int c, float lo, float hi, const svae_jpeg_spec* spec,
-                       uint64_t seed, uint64_t offset, float* out, int32_t* quality, void* stream) {
-  if (!in || !out || !spec) return fail(nullptr, SVAE_EBADARG, "jpeg_batch: null in, out or spec");
-  if (n <= 0 || h <= 0 || w <= 0) return fail(nullptr, SVAE_EBADARG, "jpeg_batch: n, h and w must be positive");
-  if (c != 1 && c != 3) return fail(nullptr, SVAE_EBADARG, "jpeg_batch: c must be 1 or 3");
-  const svae_jpeg_spec& p = *spec;
-  if (!(p.p >= 0.f && p.p <= 1.f)) return fail(nullptr, SVAE_EBADARG, "jpeg_batch: a probability outside [0, 1]");
-  if (p.q_lo < 1 || p.q_hi > 100 || p.q_lo > p.q_hi)
-    return fail(nullptr, SVAE_EBADARG, "jpeg_batch: need 1 <= q_lo <= q_hi <= 100");
-  if (p.subsample != 1 && p.subsample != 2) return fail(nullptr, SVAE_EBADARG, "jpeg_batch: subsample must be 1 or 2");
-  if (!(lo < hi)) return fail(nullptr, SVAE_EBADARG, "jpeg_batch: lo >= hi");
-  if ((int64_t)h * w * c > 2147483647LL)
-    return fail(nullptr, SVAE_EBADCONFIG, "jpeg_batch: at most 2^31 - 1 elements per image");
-  JpegArgs a{};
-  a.in = in; a.out = out; a.quality = quality;
-  a.n = n; a.h = h; a.w = w; a.c = c;
-  a.thr = prob_threshold(p.p);
-  a.q_lo = p.q_lo; a.q_hi = p.q_hi; a.subsample = c == 3 ? p.subsample : 1;
-  a.lo = lo;
-  a.qscale = (float)(((double)hi - (double)lo) / 255.0);
-  a.qinv = (float)(255.0 / ((double)hi - (double)lo));
-  a.seed = seed; a.offset = offset;
-  jpeg_batch(a, (hipStream_t)stream);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
-}
-
-// ---- overlapping tiles (tiles.hip) ----
-static int tile_count(int L, int t, int s) { return (int)(((int64_t)L - t + s - 1) / s) + 1; }
-
-// the largest sum of window weights w1(p) = min(p + 1, t - p) over the tiles covering one position of an axis
-// (exact = false: an upper bound in O(1): at most ceil(t / s) + 1 tiles cover a position, each with at most ceil(t / 2))
-static int64_t tile_axis_weight(int L, int t, int s, bool exact) {
-  const int k = tile_count(L, t, s);
-  if (!exact) return std::min<int64_t>(k, ((int64_t)t + s - 1) / s + 1) * (((int64_t)t + 1) / 2);
-  int64_t best = 0;
-  for (int64_t x = 0; x < L; ++x) {
-    int64_t hi = x >= (int64_t)L - t ? k - 1 : x / s, lo = x < t ? 0 : (x - t) / s + 1, sum = 0;
-    if (lo > k - 1) lo = k - 1;
-    for (int64_t i = lo; i <= hi; ++i) {
-      const int64_t p = x - std::min<int64_t>(i * s, (int64_t)L - t);
-      sum += std::min<int64_t>(p + 1, t - p);
-    }
-    best = std::max(best, sum);
-  }
-  return best;
-}
-
-// the checks the two tile ops share; fills g.  0, or the code fail() returned
-static int tile_geometry(const char* op, int nimg, int H, int W, int c, int th, int tw, int sy, int sx, TileGeom& g) {
-  const std::string who(op);
-  if (nimg <= 0 || H <= 0 || W <= 0 || c <= 0 || th <= 0 || tw <= 0 || sy <= 0 || sx <= 0)
-    return fail(nullptr, SVAE_EBADARG, who + ": nimg, H, W, c, th, tw, sy and sx must be positive");
-  if (th > H || tw > W) return fail(nullptr, SVAE_EBADARG, who + ": the tile exceeds the image");
-  if (sy > th || sx > tw) return fail(nullptr, SVAE_EBADARG, who + ": the stride exceeds the tile");
-  g.nimg = nimg; g.H = H; g.W = W; g.c = c; g.th = th; g.tw = tw; g.sy = sy; g.sx = sx;
-  g.ky = tile_count(H, th, sy); g.kx = tile_count(W, tw, sx);
-  g.n_tiles = (long long)nimg * g.ky * g.kx;
-  return 0;
-}
-
-static int tile_sizes(const char* op, const TileGeom& g) {
-  if ((int64_t)g.th * g.tw * g.c > 2147483647LL || (int64_t)g.H * g.W * g.c > 2147483647LL)
-    return fail(nullptr, SVAE_EBADCONFIG, std::string(op) + ": at most 2^31 - 1 elements per tile and per image");
-  return 0;
-}
-
-int svae_op_extract_tiles(const void* images, int data_u8, int nimg, int H, int W, int c, int th, int tw, int sy,
-                          int sx, float lo, float hi, int64_t first, int64_t count, float* tiles, void* stream) {
-  if (!images || !tiles) return fail(nullptr, SVAE_EBADARG, "extract_tiles: null images or tiles");
-  ExtractTilesArgs a{};
-  if (int rc = tile_geometry("extract_tiles", nimg, H, W, c, th, tw, sy, sx, a.g)) return rc;
-  if (count <= 0) return fail(nullptr, SVAE_EBADARG, "extract_tiles: count must be positive");
-  if (first < 0 || first >= a.g.n_tiles)
-    return fail(nullptr, SVAE_EBADARG, "extract_tiles: first must be in [0, n_tiles)");
-  if (data_u8 && !(lo < hi)) return fail(nullptr, SVAE_EBADARG, "extract_tiles: lo >= hi with uint8 images");
-  if (int rc = tile_sizes("extract_tiles", a.g)) return rc;
-  a.images = images; a.data_u8 = data_u8 ? 1 : 0;
-  a.lo = lo; a.qscale = (float)(((double)hi - (double)lo) / 255.0);
-  a.first = first; a.count = count; a.tiles = tiles;
-  extract_tiles(a, (hipStream_t)stream);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
-}
-
-int svae_op_blend_tiles(const float* tiles, int nstack, int64_t stack_stride, int nimg, int H, int W, int c, int th,
-                        int tw, int sy, int sx, const void* source, int source_u8, const uint8_t* known, float lo,
-                        float hi, float* out, uint8_t* out_u8, void* stream) {
-  if (!tiles) return fail(nullptr, SVAE_EBADARG, "blend_tiles: null tiles");
-  if (!out && !out_u8) return fail(nullptr, SVAE_EBADARG, "blend_tiles: out and out_u8 are both null");
-  if ((known != nullptr) != (source != nullptr))
-    return fail(nullptr, SVAE_EBADARG, "blend_tiles: known and source come together");
-  BlendTilesArgs a{};
-  if (int rc = tile_geometry("blend_tiles", nimg, H, W, c, th, tw, sy, sx, a.g)) return rc;
-  if (nstack <= 0) return fail(nullptr, SVAE_EBADARG, "blend_tiles: nstack must be positive");
-  if (stack_stride < 0 || (unsigned __int128)stack_stride < (unsigned __int128)a.g.n_tiles * th * tw * c)
-    return fail(nullptr, SVAE_EBADARG, "blend_tiles: stack_stride is smaller than a set of tiles");
-  if ((out_u8 || (source && source_u8)) && !(lo < hi))
-    return fail(nullptr, SVAE_EBADARG, "blend_tiles: lo >= hi with a uint8 source or output");
-  if (int rc = tile_sizes("blend_tiles", a.g)) return rc;
-  const auto reaches = [&](bool exact) {  // both factors < 2^31 * 2^30: the comparison is made in fp64
-    return (double)tile_axis_weight(H, th, sy, exact) * (double)tile_axis_weight(W, tw, sx, exact) >= 536870912.0;
-  };
-  if (reaches(false) && reaches(true))
-    return fail(nullptr, SVAE_EBADCONFIG, "blend_tiles: the weight sum of a pixel reaches 2^29");
-  a.tiles = tiles; a.nstack = nstack; a.stack_stride = stack_stride;
-  a.source = source; a.source_u8 = source_u8 ? 1 : 0; a.known = known;
-  a.lo = lo;
-  a.qscale = (float)(((double)hi - (double)lo) / 255.0);
-  a.qinv = (float)(255.0 / ((double)hi - (double)lo));
-  a.out = out; a.out_u8 = out_u8;
-  blend_tiles(a, (hipStream_t)stream);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
-}
-
-int64_t svae_op_stats_plan(const int64_t* offsets, const int64_t* lengths, int32_t n_seg, int64_t* table,
-                           int64_t cap_words) {
-  if (n_seg < 0 || (n_seg > 0 && (!offsets || !lengths)) || cap_words < 0)
-    return fail(nullptr, SVAE_EBADARG, "stats_plan: null segments or a negative count");
-  const long long n = stats_plan((const long long*)offsets, (const long long*)lengths, n_seg, (long long*)table,
-                                 cap_words);
-  if (n == -1)
-    return fail(nullptr, SVAE_EBADARG, "stats_plan: segments must be non-negative, ascending and disjoint");
-  if (n == -2) {
-    const long long nc = stats_plan((const long long*)offsets, (const long long*)lengths, n_seg, nullptr, 0);
-    return fail(nullptr, SVAE_EBADARG, "stats_plan: the table holds " + std::to_string((long long)cap_words) +
-                                           " words, the plan needs " + std::to_string(stats_plan_words(n_seg, nc)));
-  }
-  return n;
-}
-
-int svae_op_tensor_stats(const float* x, const int64_t* plan, int32_t n_seg, int64_t n_chunks, float c,
-                         double* partials, double* out, void* stream) {
-  if (!x || !plan || !partials || !out) return fail(nullptr, SVAE_EBADARG, "tensor_stats: null pointer");
-  if (n_seg < 0 || n_chunks < 0) return fail(nullptr, SVAE_EBADARG, "tensor_stats: negative count");
-  if (!(c >= 0.f)) return fail(nullptr, SVAE_EBADARG, "tensor_stats: the clamp must be >= 0 (+inf: none)");
-  tensor_stats(x, (const long long*)plan, n_seg, n_chunks, c, partials, out, (hipStream_t)stream);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
-}
-
-int svae_op_image_metrics(const float* x, int n, const float* y, int ny, int h, int w, int c, float data_range,
-                          double* out, void* stream) {
-  if (!x || !y || !out) return fail(nullptr, SVAE_EBADARG, "image_metrics: null pointer");
-  if (n <= 0 || ny <= 0 || c <= 0) return fail(nullptr, SVAE_EBADARG, "image_metrics: n, ny and c must be positive");
-  if (n % ny != 0) return fail(nullptr, SVAE_EBADARG, "image_metrics: n must be a multiple of ny");
-  if (h < SVAE_SSIM_WINDOW || w < SVAE_SSIM_WINDOW)
-    return fail(nullptr, SVAE_EBADARG, "image_metrics: h and w must hold one " + std::to_string(SVAE_SSIM_WINDOW) +
-                                           "-wide window");
-  if (!(data_range > 0.f)) return fail(nullptr, SVAE_EBADARG, "image_metrics: data_range must be > 0");
-  image_metrics(x, n, y, ny, h, w, c, data_range, out, (hipStream_t)stream);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
-}
-
-int svae_op_mixture_logdensity(const float* z, int64_t nq, int64_t ldz, const float* mu, const float* sigma,
-                               int64_t nm, int64_t ldm, int d, const int32_t* seg, int n_seg, double* out,
-                               void* stream) {
-  if (!z || !mu || !sigma || !seg || !out) return fail(nullptr, SVAE_EBADARG, "mixture_logdensity: null pointer");
-  if (nq <= 0 || nm <= 0 || d <= 0 || n_seg <= 0)
-    return fail(nullptr, SVAE_EBADARG, "mixture_logdensity: nq, nm, d and n_seg must be positive");
-  if (d > SVAE_LATENTS_MAX_DIM || n_seg > SVAE_LATENTS_MAX_SEGMENTS || nq > 2147483647LL)
-    return fail(nullptr, SVAE_EBADCONFIG, "mixture_logdensity: at most " + std::to_string(SVAE_LATENTS_MAX_DIM) +
-                                              " dimensions, " + std::to_string(SVAE_LATENTS_MAX_SEGMENTS) +
-                                              " segments and 2^31 - 1 query rows");
-  if (ldz < d || ldm < d) return fail(nullptr, SVAE_EBADARG, "mixture_logdensity: a leading dimension below d");
-  for (int i = 0; i < n_seg; ++i) {
-    const int64_t off = seg[2 * i], len = seg[2 * i + 1];
-    if (off < 0 || len < 1 || off + len > d)
-      return fail(nullptr, SVAE_EBADARG, "mixture_logdensity: segment " + std::to_string(i) + " is not inside [0, d)");
-  }
-  mixture_logdensity(z, nq, ldz, mu, sigma, nm, ldm, seg, n_seg, out, (hipStream_t)stream);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
-}
-
-static bool pairwise_shape_ok(int64_t n, const int64_t* m, int n_groups, int n_bw) {
-  if (!m || n <= 0 || n_groups <= 0 || n_groups > SVAE_PAIRWISE_MAX_GROUPS || n_bw < 0 || n_bw > SVAE_PAIRWISE_MAX_BW)
-    return false;
-  int64_t tiles = 0;
-  for (int g = 0; g < n_groups; ++g) {
-    if (m[g] <= 0) return false;
-    tiles += (m[g] + SVAE_PAIRWISE_TILE_COLS - 1) / SVAE_PAIRWISE_TILE_COLS;
-  }
-  return tiles <= 2147483647LL && (n + SVAE_PAIRWISE_TILE_ROWS - 1) / SVAE_PAIRWISE_TILE_ROWS <= 65535;
-}
-
-int64_t svae_op_pairwise_scratch_bytes(int64_t n, const int64_t* m, int n_groups, int n_bw) {
-  if (!pairwise_shape_ok(n, m, n_groups, n_bw)) return -1;
-  long long mm[SVAE_PAIRWISE_MAX_GROUPS];
-  for (int g = 0; g < n_groups; ++g) mm[g] = m[g];
-  return pairwise_scratch_bytes(n, mm, n_groups, n_bw);
-}
-
-int svae_op_pairwise_stats(const float* x, int64_t n, int64_t ldx, const float* const* y, const int64_t* m,
-                           const int64_t* ldy, int n_groups, int64_t d, int self_group,
-                           const double* inv_two_sigma2, int n_bw, double* ksum, double* nn_d2, int64_t* nn_idx,
-                           void* scratch, void* stream) {
-  if (!x || !y || !m || !ldy) return fail(nullptr, SVAE_EBADARG, "pairwise_stats: null pointer");
-  if (n <= 0 || d <= 0 || n_groups <= 0 || n_bw < 0)
-    return fail(nullptr, SVAE_EBADARG, "pairwise_stats: n, d and n_groups must be positive, n_bw not negative");
-  if (n_groups > SVAE_PAIRWISE_MAX_GROUPS || n_bw > SVAE_PAIRWISE_MAX_BW)
-    return fail(nullptr, SVAE_EBADCONFIG, "pairwise_stats: at most " + std::to_string(SVAE_PAIRWISE_MAX_GROUPS) +
-                                              " groups and " + std::to_string(SVAE_PAIRWISE_MAX_BW) + " bandwidths");
-  if ((n_bw == 0) != (ksum == nullptr))
-    return fail(nullptr, SVAE_EBADARG, "pairwise_stats: ksum goes with n_bw > 0 and only with it");
-  if ((nn_d2 == nullptr) != (nn_idx == nullptr))
-    return fail(nullptr, SVAE_EBADARG, "pairwise_stats: nn_d2 and nn_idx come together");
-  if (!ksum && !nn_d2) return fail(nullptr, SVAE_EBADARG, "pairwise_stats: nothing to compute");
-  if (n_bw > 0 && !inv_two_sigma2) return fail(nullptr, SVAE_EBADARG, "pairwise_stats: null bandwidths");
-  if (ldx < d) return fail(nullptr, SVAE_EBADARG, "pairwise_stats: ldx below d");
-  for (int g = 0; g < n_groups; ++g) {
-    if (!y[g]) return fail(nullptr, SVAE_EBADARG, "pairwise_stats: null group " + std::to_string(g));
-    if (m[g] <= 0) return fail(nullptr, SVAE_EBADARG, "pairwise_stats: group " + std::to_string(g) + " is empty");
-    if (ldy[g] < d) return fail(nullptr, SVAE_EBADARG, "pairwise_stats: ldy below d in group " + std::to_string(g));
-  }
-  for (int l = 0; l < n_bw; ++l)
-    if (!(inv_two_sigma2[l] > 0.0) || !std::isfinite(inv_two_sigma2[l]))
-      return fail(nullptr, SVAE_EBADARG, "pairwise_stats: bandwidth " + std::to_string(l) + " is not positive and finite");
-  if (self_group >= n_groups) return fail(nullptr, SVAE_EBADARG, "pairwise_stats: self_group names no group");
-  if (self_group >= 0 && (n != m[self_group] || x != y[self_group]))
-    return fail(nullptr, SVAE_EBADARG, "pairwise_stats: self_group needs x == y[self_group] and n == m[self_group]");
-  if (d > 2147483647LL || !pairwise_shape_ok(n, m, n_groups, n_bw))
-    return fail(nullptr, SVAE_EBADCONFIG, "pairwise_stats: d above 2^31 - 1, or too many row or column tiles");
-  if (!scratch) return fail(nullptr, SVAE_EBADARG, "pairwise_stats: null scratch");
-  long long mm[SVAE_PAIRWISE_MAX_GROUPS], ll[SVAE_PAIRWISE_MAX_GROUPS];
-  for (int g = 0; g < n_groups; ++g) {
-    mm[g] = m[g];
-    ll[g] = ldy[g];
-  }
-  pairwise_stats(x, n, ldx, y, mm, ll, n_groups, (int)d, self_group < 0 ? -1 : self_group, inv_two_sigma2, n_bw, ksum,
-                 nn_d2, (long long*)nn_idx, scratch, (hipStream_t)stream);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
-}
-
-int svae_op_power_spectrum(const float* x, int n, const float* y, int ny, int h, int w, int c, const double* win_y,
-                           const double* win_x, const double* tw_y, const double* tw_x, const int32_t* bin, int n_bins,
-                           double* out, int64_t* nonfinite, void* stream) {
-  if (!x || !win_y || !win_x || !tw_y || !tw_x || !bin || !out)
-    return fail(nullptr, SVAE_EBADARG, "power_spectrum: null pointer");
-  if (n <= 0 || ny <= 0 || c <= 0 || n_bins <= 0)
-    return fail(nullptr, SVAE_EBADARG, "power_spectrum: n, ny, c and n_bins must be positive");
-  if (h < 2 || w < 2) return fail(nullptr, SVAE_EBADARG, "power_spectrum: h and w must be at least 2");
-  if (y && n % ny != 0) return fail(nullptr, SVAE_EBADARG, "power_spectrum: n must be a multiple of ny");
-  if (h > SVAE_SPECTRUM_MAX_DIM || w > SVAE_SPECTRUM_MAX_DIM || n_bins > SVAE_SPECTRUM_MAX_BINS)
-    return fail(nullptr, SVAE_EBADCONFIG, "power_spectrum: at most " + std::to_string(SVAE_SPECTRUM_MAX_DIM) +
-                                              " rows and columns and " + std::to_string(SVAE_SPECTRUM_MAX_BINS) +
-                                              " bins");
-  if ((int64_t)h * w * c > 2147483647LL || (int64_t)n * c > 2147483647LL)
-    return fail(nullptr, SVAE_EBADCONFIG, "power_spectrum: h * w * c or n * c above 2^31 - 1");
-  hipError_t e = power_spectrum(x, n, y, ny, h, w, c, win_y, win_x, tw_y, tw_x, bin, n_bins, out,
-                                (long long*)nonfinite, (hipStream_t)stream);
-  return e == hipSuccess ? 0 : fail(nullptr, SVAE_EHIP, hipGetErrorString(e));
 }
 
 }  // extern "C"

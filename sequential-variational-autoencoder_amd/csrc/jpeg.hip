@@ -3,8 +3,8 @@
 // quality-scaled Annex K quantiser, the inverse transform, chroma replication, RGB and the dequantisation of
 // svae_op_make_batch.  No entropy coding: only the decoded pixels exist.
 //
-// Per-image draws are Philox4x32-10 under the key (lo32(seed), hi32(seed)) with the counter words (offset + b in
-// c0 / c1, c2 = 5, c3 = 0): stream 5 is one neither make_batch (0 .. 2), degrade_batch (3) nor crop_batch (4) uses.
+// The per-image draw is philox.h's philox_image on the stream PHILOX_JPEG, block 0: image b is compressed iff word 0
+// is below thr, at quality q_lo + mulhi(word 1, q_hi - q_lo + 1).  The dequantisation is pixel.h's.
 // Every sum has a fixed order and every operation is rounded on its own (contract(off)), so the result depends on
 // the arguments alone: not on the launch and not on the path (16-byte / scalar) the alignment selects.
 //
@@ -26,13 +26,25 @@
 // LDS layout: an 8 x 8 block keeps its rows 12 floats apart (a row is two 16-byte accesses) and blocks lie 104
 // floats apart.  The column walks of step 4 (lane (block, u) at block * 104 + y * 12 + u) then fall on 32 different
 // banks for 32 consecutive lanes (104 mod 32 = 8), where rows 8 apart would put eight lanes on one bank.
+// svae_op_jpeg_batch, with its argument checks and the launch, ends the file.
 #include <cstdint>
 
 #include "common.h"
-#include "kernels.h"
+#include "opentry.h"
 #include "philox.h"
+#include "pixel.h"
 
 namespace {
+
+// in [n,h,w,c] -> out (may be in), quality [n] (may be nullptr), one launch
+struct JpegArgs {
+  const float* in; float* out; int* quality;
+  int n, h, w, c;
+  unsigned thr;
+  int q_lo, q_hi, subsample;         // subsample 2 only with c == 3 (the entry point makes it 1 for c == 1)
+  float lo, qscale, qinv;            // qscale = (hi - lo) / 255, qinv = 255 / (hi - lo), each rounded to fp32
+  unsigned long long seed, offset;
+};
 
 constexpr int JP_THREADS = 128;
 constexpr int JP_TILE = 16;
@@ -140,10 +152,9 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_batch_kernel(JpegArgs a, int 
     const int nr = min(JP_TILE, a.h - i0), nc = min(JP_TILE, a.w - j0), nf = nc * c;
     // the image's draws, once per block
     if (tid == 0) {
-      const unsigned long long ctr = a.offset + (unsigned long long)b;
-      unsigned w0 = (unsigned)ctr, w1 = (unsigned)(ctr >> 32), w2 = 5, w3 = 0;
-      philox(w0, w1, w2, w3, (unsigned)a.seed, (unsigned)(a.seed >> 32));
-      const int q = w0 < a.thr ? a.q_lo + (int)__umulhi(w1, (unsigned)(a.q_hi - a.q_lo + 1)) : 0;
+      unsigned w[4];
+      philox_image(a.seed, a.offset, b, PHILOX_JPEG, 0, w);
+      const int q = w[0] < a.thr ? a.q_lo + (int)__umulhi(w[1], (unsigned)(a.q_hi - a.q_lo + 1)) : 0;
       jp_hdr[0] = q;
       if (a.quality && t == 0) a.quality[b] = q;
     }
@@ -264,8 +275,7 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_batch_kernel(JpegArgs a, int 
           float* px = raw + ty * JP_RAW + tx * c;
           const float Y = blk[jp_at16(0, ty, tx)];
           if (c == 1) {
-            const float pr = Y * a.qscale;
-            px[0] = a.lo + pr;
+            px[0] = u8_dequant(Y, a.lo, a.qscale);
           } else {
             float Cb, Cr;
             if (sub2) {
@@ -280,10 +290,9 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_batch_kernel(JpegArgs a, int 
             const float g0 = 0.344136286f * db, g1 = 0.714136286f * dr;
             const float b0 = 1.772f * db;
             const float R = jp_level(Y + r0), G = jp_level((Y - g0) - g1), B = jp_level(Y + b0);
-            const float pr = R * a.qscale, pg = G * a.qscale, pb = B * a.qscale;
-            px[0] = a.lo + pr;
-            px[1] = a.lo + pg;
-            px[2] = a.lo + pb;
+            px[0] = u8_dequant(R, a.lo, a.qscale);
+            px[1] = u8_dequant(G, a.lo, a.qscale);
+            px[2] = u8_dequant(B, a.lo, a.qscale);
           }
         }
         __syncthreads();
@@ -306,13 +315,36 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_batch_kernel(JpegArgs a, int 
   }
 }
 
-inline bool jp_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
-void jpeg_batch(const JpegArgs& a, hipStream_t s) {
-  const long long items = (long long)a.n * ((a.h + JP_TILE - 1) / JP_TILE) * ((a.w + JP_TILE - 1) / JP_TILE);
-  const int row4 = (a.w * a.c) % 4 == 0;
+extern "C" {
+
+int svae_op_jpeg_batch(const float* in, int n, int h, int w, int c, float lo, float hi, const svae_jpeg_spec* spec,
+                       uint64_t seed, uint64_t offset, float* out, int32_t* quality, void* stream) {
+  if (!in || !out || !spec) return op_fail(SVAE_EBADARG, "jpeg_batch: null in, out or spec");
+  if (n <= 0 || h <= 0 || w <= 0) return op_fail(SVAE_EBADARG, "jpeg_batch: n, h and w must be positive");
+  if (c != 1 && c != 3) return op_fail(SVAE_EBADARG, "jpeg_batch: c must be 1 or 3");
+  const svae_jpeg_spec& p = *spec;
+  if (!(p.p >= 0.f && p.p <= 1.f)) return op_fail(SVAE_EBADARG, "jpeg_batch: a probability outside [0, 1]");
+  if (p.q_lo < 1 || p.q_hi > 100 || p.q_lo > p.q_hi)
+    return op_fail(SVAE_EBADARG, "jpeg_batch: need 1 <= q_lo <= q_hi <= 100");
+  if (p.subsample != 1 && p.subsample != 2) return op_fail(SVAE_EBADARG, "jpeg_batch: subsample must be 1 or 2");
+  if (!(lo < hi)) return op_fail(SVAE_EBADARG, "jpeg_batch: lo >= hi");
+  if ((int64_t)h * w * c > 2147483647LL)
+    return op_fail(SVAE_EBADCONFIG, "jpeg_batch: at most 2^31 - 1 elements per image");
+  JpegArgs a{};
+  a.in = in; a.out = out; a.quality = quality;
+  a.n = n; a.h = h; a.w = w; a.c = c;
+  a.thr = prob_threshold(p.p);
+  a.q_lo = p.q_lo; a.q_hi = p.q_hi; a.subsample = c == 3 ? p.subsample : 1;
+  const QScale q = quant_scale(lo, hi);
+  a.lo = lo; a.qscale = q.qscale; a.qinv = q.qinv;
+  a.seed = seed; a.offset = offset;
+  const long long items = (long long)n * ((h + JP_TILE - 1) / JP_TILE) * ((w + JP_TILE - 1) / JP_TILE);
+  const int row4 = (w * c) % 4 == 0;
   hipLaunchKernelGGL(jpeg_batch_kernel, dim3((unsigned)(items < JP_GRID_CAP ? items : JP_GRID_CAP)),
-                     dim3(JP_THREADS), 0, s, a, jp_al16(a.in) && row4 ? 1 : 0, jp_al16(a.out) && row4 ? 1 : 0);
+                     dim3(JP_THREADS), 0, (hipStream_t)stream, a, al16(in) && row4 ? 1 : 0, al16(out) && row4 ? 1 : 0);
+  return op_done();
 }
+
+}  // extern "C"

@@ -336,116 +336,8 @@ int dense_kw(const FwdArgs& a, int ks, hipStream_t s);  // returns ks
 void bf16_to_f32(const void* src, float* dst, long long n, hipStream_t s);  // debug copies of bf16 activations
 void fill_f32(float* p, long long n, float v, hipStream_t s);
 void philox_normal(float* out, long long n, unsigned long long seed, unsigned long long offset, hipStream_t s);
-// ---- training batch (batch.hip): row gather + dequantisation + denoising corruption, one launch ----
-// row b of the batch = data[idx ? idx[b] : start + b] (uint8 or fp32 rows of per_image elements);
-// target = lo + u8 * qscale (fp32 rows: as they are); input = clip(target * keep + salt + scale * N(0,1), lo, hi)
-// with keep = (pepper word >= thr_pepper), salt = (salt word < thr_salt), Philox counters offset + e / 4
-struct MakeBatchArgs {
-  const void* data; int data_u8;
-  const int* idx; long long start;
-  long long per_image, total;        // total = n * per_image
-  float lo, hi, qscale, scale;       // qscale = (hi - lo) / 255
-  unsigned thr_pepper, thr_salt;
-  unsigned long long seed, offset;
-  float* target; float* input;       // either may be nullptr
-};
-void make_batch(const MakeBatchArgs& a, hipStream_t s);
-// ---- structured corruptions (degrade.hip): blur, box down-sampling, cut-out, then make_batch's pixel noise ----
-// target [n,h,w,c] -> input (and mask [n,h,w], may be nullptr), one launch.  Per-image draws: Philox counter
-// (offset + b, c2 = 3, c3 = block): block 0 the three gates and sigma, block 1 + k box k.  nz carries the pixel noise
-// (lo, hi, scale, thr_pepper, thr_salt, seed, offset: the fields mb_corrupt reads).
-struct DegradeArgs {
-  const float* target; float* input; float* mask;
-  int n, h, w, c;
-  unsigned thr_blur, thr_down, thr_cut;
-  float sigma_lo, sigma_hi, fill;
-  int factor, boxes, min_side, max_side;
-  int rmax;                          // min(ceil(3 sigma_hi), 12), 0 without blur: what the LDS band is sized for
-  MakeBatchArgs nz;
-};
-// bytes of LDS the band kernel needs for bands of `band` rows (degrade_batch falls back to global memory above 64 KB)
-long long degrade_lds_bytes(const DegradeArgs& a, int band);
-void degrade_batch(const DegradeArgs& a, hipStream_t s);
-// ---- overlapping tiles (tiles.hip): svae_op_extract_tiles and svae_op_blend_tiles ----
-// per axis: k = ceil((L - t) / s) + 1 tiles, tile i at min(i s, L - t); tile id (m ky + i) kx + j
-struct TileGeom {
-  int nimg, H, W, c, th, tw, sy, sx;
-  int ky, kx;                        // tiles per axis
-  long long n_tiles;                 // nimg * ky * kx
-};
-struct ExtractTilesArgs {
-  TileGeom g;
-  const void* images; int data_u8;
-  float lo, qscale;                  // qscale = (hi - lo) / 255 rounded to fp32 (make_batch's)
-  long long first, count;
-  float* tiles;
-};
-struct BlendTilesArgs {
-  TileGeom g;
-  const float* tiles; int nstack; long long stack_stride;
-  const void* source; int source_u8; const unsigned char* known;   // source and known: both or neither
-  float lo, qscale, qinv;            // qinv = 255 / (hi - lo) rounded to fp32
-  float* out; unsigned char* out_u8; // either may be nullptr
-};
-void extract_tiles(const ExtractTilesArgs& a, hipStream_t s);
-void blend_tiles(const BlendTilesArgs& a, hipStream_t s);
-// ---- random crops (crops.hip): svae_op_crop_batch ----
-// row b of the batch = the h x w window at (y0, x0) of image m, box-averaged by s and mapped by symmetry g, with
-// (m, s, g, y0, x0) = crops[b], or drawn from Philox counter (offset + b, c2 = 4, c3 = block) when crops == nullptr
-struct CropArgs {
-  const void* images; int data_u8;
-  int nimg, H, W, c, h, w;
-  int n_scales, scales[4], smax;     // smax: the largest listed scale (what the LDS patch is sized for)
-  int symmetries;
-  const int* crops;
-  unsigned long long seed, offset;
-  int n;
-  float lo, qscale;                  // qscale = (hi - lo) / 255 rounded to fp32 (make_batch's)
-  float* target; unsigned char* target_u8; int* meta;   // target or target_u8 may be nullptr, meta may be
-};
-void crop_batch(const CropArgs& a, hipStream_t s);
-// ---- JPEG artefacts (jpeg.hip): svae_op_jpeg_batch ----
-// in [n,h,w,c] -> out (may be in), quality [n] (may be nullptr), one launch.  Image b is compressed iff word a0 of
-// Philox counter (offset + b, c2 = 5, c3 = 0) is below thr, at quality q_lo + mulhi(a1, q_hi - q_lo + 1)
-struct JpegArgs {
-  const float* in; float* out; int* quality;
-  int n, h, w, c;
-  unsigned thr;
-  int q_lo, q_hi, subsample;         // subsample 2 only with c == 3 (the entry point makes it 1 for c == 1)
-  float lo, qscale, qinv;            // qscale = (hi - lo) / 255, qinv = 255 / (hi - lo), each rounded to fp32
-  unsigned long long seed, offset;
-};
-void jpeg_batch(const JpegArgs& a, hipStream_t s);
-// ---- segmented statistics (stats.hip): the eight fp64 columns of svae_op_tensor_stats per segment ----
-// plan table (int64 words): [0, n_seg] the index of every segment's first chunk (entry n_seg = n_chunks), then
-// per chunk (begin, segment << 32 | length).  stats_plan returns the chunk count (table == nullptr: count only),
-// -1 for a negative, unordered or overlapping segment, -2 when cap_words < stats_plan_words().
-inline long long stats_plan_words(int n_seg, long long n_chunks) { return (long long)n_seg + 1 + 2 * n_chunks; }
-long long stats_plan(const long long* offsets, const long long* lengths, int n_seg, long long* table,
-                     long long cap_words);
-// part: n_chunks * 8 doubles; out: n_seg * 8 doubles; at most two launches on s
-void tensor_stats(const float* x, const long long* plan, int n_seg, long long n_chunks, float c, double* part,
-                  double* out, hipStream_t s);
-// ---- image metrics (metrics.hip): the four fp64 columns of svae_op_image_metrics per image, one launch on s ----
-// image i of x [n,h,w,c] against image i % ny of y; arguments as checked by the entry point (h, w >= 11)
-void image_metrics(const float* x, int n, const float* y, int ny, int h, int w, int c, float data_range, double* out,
-                   hipStream_t s);
-// ---- mixture log-density (latents.hip): svae_op_mixture_logdensity's [nq][n_seg] fp64 table, launches on s ----
-// seg: host (offset, length) pairs; arguments as checked by the entry point
-void mixture_logdensity(const float* z, long long nq, long long ldz, const float* mu, const float* sigma,
-                        long long nm, long long ldm, const int* seg, int n_seg, double* out, hipStream_t s);
-// ---- pairwise-distance statistics (pairwise.hip): svae_op_pairwise_stats, launches on s ----
-// y, m, ldy, inv_two_sigma2: host arrays; arguments as checked by the entry point
-long long pairwise_scratch_bytes(long long n, const long long* m, int n_groups, int n_bw);
-void pairwise_stats(const float* x, long long n, long long ldx, const float* const* y, const long long* m,
-                    const long long* ldy, int n_groups, int d, int self_group, const double* inv_two_sigma2,
-                    int n_bw, double* ksum, double* nn_d2, long long* nn_idx, void* scratch, hipStream_t s);
-// ---- binned power spectra (spectrum.hip): svae_op_power_spectrum's [n][c][2][n_bins] fp64 table, one launch on s ----
-// y == nullptr: plane 0 only; nonfinite [n][c] may be nullptr; arguments as checked by the entry point; returns the
-// error of the once-per-device dynamic-LDS attribute or of the launch
-hipError_t power_spectrum(const float* x, int n, const float* y, int ny, int h, int w, int c, const double* win_y,
-                          const double* win_x, const double* tw_y, const double* tw_x, const int* bin, int n_bins,
-                          double* out, long long* nonfinite, hipStream_t s);
+// ---- the trainer and report ops (batch, degrade, crops, jpeg, tiles, stats, metrics, latents, pairwise, spectrum) keep
+// their argument structs, launchers and C entry points in their own .hip (opentry.h): nothing of theirs is declared here
 // ---- Polyak average (ema.hip): ema[i] -= omd * (ema[i] - w[i]) over [0, n), three fp32 roundings, one launch on s
 // (none for n <= 0 or omd == 0); any alignment of either pointer ----
 void ema_update(float* ema, const float* w, long long n, float omd, hipStream_t s);

@@ -19,12 +19,12 @@
 // The hull's width picks the instance, DMAX = 16, 64, 128 or 256 (LDS per block = (4 ML_ROWS + 20 ML_TILE) DMAX
 // bytes: 9, 36, 72, 144 KB).  The host walks the groups in order and launches every run of up to
 // ML_LAUNCH_GROUPS groups of one instance at once, its segments in the kernel's argument block.
+// svae_op_mixture_logdensity, with its argument checks, ends the file.
 #include <cmath>
 #include <cstdint>
 
 #include "common.h"
-#include "kernels.h"
-#include "svae_hip.h"
+#include "opentry.h"
 
 #pragma clang fp contract(off)
 
@@ -132,8 +132,7 @@ void ml_launch(const float* z, long long nq, long long ldz, const float* mu, con
                      sg, n_here, seg0, n_seg, out);
 }
 
-}  // namespace
-
+// seg: host (offset, length) pairs; launches on s
 void mixture_logdensity(const float* z, long long nq, long long ldz, const float* mu, const float* sigma,
                         long long nm, long long ldm, const int* seg, int n_seg, double* out, hipStream_t s) {
   int first = 0;  // the run's first segment (a multiple of ML_GROUP)
@@ -164,3 +163,29 @@ void mixture_logdensity(const float* z, long long nq, long long ldz, const float
     first += n_here;
   }
 }
+
+}  // namespace
+
+extern "C" {
+
+int svae_op_mixture_logdensity(const float* z, int64_t nq, int64_t ldz, const float* mu, const float* sigma,
+                               int64_t nm, int64_t ldm, int d, const int32_t* seg, int n_seg, double* out,
+                               void* stream) {
+  if (!z || !mu || !sigma || !seg || !out) return op_fail(SVAE_EBADARG, "mixture_logdensity: null pointer");
+  if (nq <= 0 || nm <= 0 || d <= 0 || n_seg <= 0)
+    return op_fail(SVAE_EBADARG, "mixture_logdensity: nq, nm, d and n_seg must be positive");
+  if (d > SVAE_LATENTS_MAX_DIM || n_seg > SVAE_LATENTS_MAX_SEGMENTS || nq > 2147483647LL)
+    return op_fail(SVAE_EBADCONFIG, "mixture_logdensity: at most " + std::to_string(SVAE_LATENTS_MAX_DIM) +
+                                        " dimensions, " + std::to_string(SVAE_LATENTS_MAX_SEGMENTS) +
+                                        " segments and 2^31 - 1 query rows");
+  if (ldz < d || ldm < d) return op_fail(SVAE_EBADARG, "mixture_logdensity: a leading dimension below d");
+  for (int i = 0; i < n_seg; ++i) {
+    const int64_t off = seg[2 * i], len = seg[2 * i + 1];
+    if (off < 0 || len < 1 || off + len > d)
+      return op_fail(SVAE_EBADARG, "mixture_logdensity: segment " + std::to_string(i) + " is not inside [0, d)");
+  }
+  mixture_logdensity(z, nq, ldz, mu, sigma, nm, ldm, seg, n_seg, out, (hipStream_t)stream);
+  return op_done();
+}
+
+}  // extern "C"

@@ -16,13 +16,13 @@
 //  x y along a row (taps k = 0 .. 10 in order, one fma each; the product of two fp32 values is exact in fp64),
 //  the vertical pass adds the rows k = 0 .. 10 in order.  Thread (r, q) of the 16 x 16 block owns position
 //  (r, q) of every tile and adds its SSIM values in tile order; then the same wave tree and wave order.
+// svae_op_image_metrics, with its argument checks, the window weights and the launch, ends the file.
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
 
 #include "common.h"
-#include "kernels.h"
-#include "svae_hip.h"
+#include "opentry.h"
 
 namespace {
 
@@ -172,8 +172,17 @@ __global__ __launch_bounds__(IM_THREADS) void image_metrics_kernel(const float* 
 
 }  // namespace
 
-void image_metrics(const float* x, int n, const float* y, int ny, int h, int w, int c, float data_range, double* out,
-                   hipStream_t s) {
+extern "C" {
+
+int svae_op_image_metrics(const float* x, int n, const float* y, int ny, int h, int w, int c, float data_range,
+                          double* out, void* stream) {
+  if (!x || !y || !out) return op_fail(SVAE_EBADARG, "image_metrics: null pointer");
+  if (n <= 0 || ny <= 0 || c <= 0) return op_fail(SVAE_EBADARG, "image_metrics: n, ny and c must be positive");
+  if (n % ny != 0) return op_fail(SVAE_EBADARG, "image_metrics: n must be a multiple of ny");
+  if (h < SVAE_SSIM_WINDOW || w < SVAE_SSIM_WINDOW)
+    return op_fail(SVAE_EBADARG, "image_metrics: h and w must hold one " + std::to_string(SVAE_SSIM_WINDOW) +
+                                     "-wide window");
+  if (!(data_range > 0.f)) return op_fail(SVAE_EBADARG, "image_metrics: data_range must be > 0");
   SsimWeights wt;
   double sum = 0.0;
   for (int k = 0; k < IM_WIN; ++k) {
@@ -184,6 +193,9 @@ void image_metrics(const float* x, int n, const float* y, int ny, int h, int w, 
   for (int k = 0; k < IM_WIN; ++k) wt.g[k] /= sum;
   const double L = (double)data_range;
   const double c1 = (SVAE_SSIM_K1 * L) * (SVAE_SSIM_K1 * L), c2 = (SVAE_SSIM_K2 * L) * (SVAE_SSIM_K2 * L);
-  hipLaunchKernelGGL(image_metrics_kernel, dim3((unsigned)n), dim3(IM_THREADS), 0, s, x, y, ny, h, w, c, c1, c2,
-                     wt, out);
+  hipLaunchKernelGGL(image_metrics_kernel, dim3((unsigned)n), dim3(IM_THREADS), 0, (hipStream_t)stream, x, y, ny, h, w,
+                     c, c1, c2, wt, out);
+  return op_done();
 }
+
+}  // extern "C"

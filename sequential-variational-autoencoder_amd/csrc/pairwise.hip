@@ -27,12 +27,12 @@
 //
 // A NaN or inf element, or an inner product that overflows fp32: d2 is NaN for every pair that reads it; the sums
 // carry it, and the running minimum takes the first NaN it meets and keeps it (nn_idx names that column).
+// svae_op_pairwise_scratch_bytes and svae_op_pairwise_stats, with their argument checks, end the file.
 #include <cmath>
 #include <cstdint>
 
 #include "common.h"
-#include "kernels.h"
-#include "svae_hip.h"
+#include "opentry.h"
 
 #pragma clang fp contract(off)
 
@@ -243,23 +243,22 @@ __global__ __launch_bounds__(256) void pw_reduce(long long n, PwArgs A, const do
   }
 }
 
-long long pw_tiles(const long long* m, int n_groups) {
+long long pw_tiles(const int64_t* m, int n_groups) {
   long long t = 0;
   for (int g = 0; g < n_groups; ++g) t += (m[g] + PW_C - 1) / PW_C;
   return t;
 }
 
-}  // namespace
-
 // scratch: a [n] and b [sum m] norms, then per (column tile, row) the n_bw sums, the minimum and its index
-long long pairwise_scratch_bytes(long long n, const long long* m, int n_groups, int n_bw) {
+long long pairwise_scratch_bytes(long long n, const int64_t* m, int n_groups, int n_bw) {
   long long cols = 0;
   for (int g = 0; g < n_groups; ++g) cols += m[g];
   return 8 * (n + cols) + pw_tiles(m, n_groups) * n * (8LL * n_bw + 16);
 }
 
-void pairwise_stats(const float* x, long long n, long long ldx, const float* const* y, const long long* m,
-                    const long long* ldy, int n_groups, int d, int self_group, const double* inv_two_sigma2,
+// y, m, ldy, inv_two_sigma2: host arrays; launches on s
+void pairwise_stats(const float* x, long long n, long long ldx, const float* const* y, const int64_t* m,
+                    const int64_t* ldy, int n_groups, int d, int self_group, const double* inv_two_sigma2,
                     int n_bw, double* ksum, double* nn_d2, long long* nn_idx, void* scratch, hipStream_t s) {
   PwArgs A = {};
   A.n_groups = n_groups;
@@ -295,3 +294,61 @@ void pairwise_stats(const float* x, long long n, long long ldx, const float* con
   hipLaunchKernelGGL(pw_reduce, dim3((unsigned)((n * n_groups + 255) / 256)), dim3(256), 0, s, n, A, pk, pd, pi,
                      ksum, nn_d2, nn_idx);
 }
+
+bool pairwise_shape_ok(int64_t n, const int64_t* m, int n_groups, int n_bw) {
+  if (!m || n <= 0 || n_groups <= 0 || n_groups > SVAE_PAIRWISE_MAX_GROUPS || n_bw < 0 || n_bw > SVAE_PAIRWISE_MAX_BW)
+    return false;
+  int64_t tiles = 0;
+  for (int g = 0; g < n_groups; ++g) {
+    if (m[g] <= 0) return false;
+    tiles += (m[g] + SVAE_PAIRWISE_TILE_COLS - 1) / SVAE_PAIRWISE_TILE_COLS;
+  }
+  return tiles <= 2147483647LL && (n + SVAE_PAIRWISE_TILE_ROWS - 1) / SVAE_PAIRWISE_TILE_ROWS <= 65535;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t svae_op_pairwise_scratch_bytes(int64_t n, const int64_t* m, int n_groups, int n_bw) {
+  if (!pairwise_shape_ok(n, m, n_groups, n_bw)) return -1;
+  return pairwise_scratch_bytes(n, m, n_groups, n_bw);
+}
+
+int svae_op_pairwise_stats(const float* x, int64_t n, int64_t ldx, const float* const* y, const int64_t* m,
+                           const int64_t* ldy, int n_groups, int64_t d, int self_group,
+                           const double* inv_two_sigma2, int n_bw, double* ksum, double* nn_d2, int64_t* nn_idx,
+                           void* scratch, void* stream) {
+  if (!x || !y || !m || !ldy) return op_fail(SVAE_EBADARG, "pairwise_stats: null pointer");
+  if (n <= 0 || d <= 0 || n_groups <= 0 || n_bw < 0)
+    return op_fail(SVAE_EBADARG, "pairwise_stats: n, d and n_groups must be positive, n_bw not negative");
+  if (n_groups > SVAE_PAIRWISE_MAX_GROUPS || n_bw > SVAE_PAIRWISE_MAX_BW)
+    return op_fail(SVAE_EBADCONFIG, "pairwise_stats: at most " + std::to_string(SVAE_PAIRWISE_MAX_GROUPS) +
+                                        " groups and " + std::to_string(SVAE_PAIRWISE_MAX_BW) + " bandwidths");
+  if ((n_bw == 0) != (ksum == nullptr))
+    return op_fail(SVAE_EBADARG, "pairwise_stats: ksum goes with n_bw > 0 and only with it");
+  if ((nn_d2 == nullptr) != (nn_idx == nullptr))
+    return op_fail(SVAE_EBADARG, "pairwise_stats: nn_d2 and nn_idx come together");
+  if (!ksum && !nn_d2) return op_fail(SVAE_EBADARG, "pairwise_stats: nothing to compute");
+  if (n_bw > 0 && !inv_two_sigma2) return op_fail(SVAE_EBADARG, "pairwise_stats: null bandwidths");
+  if (ldx < d) return op_fail(SVAE_EBADARG, "pairwise_stats: ldx below d");
+  for (int g = 0; g < n_groups; ++g) {
+    if (!y[g]) return op_fail(SVAE_EBADARG, "pairwise_stats: null group " + std::to_string(g));
+    if (m[g] <= 0) return op_fail(SVAE_EBADARG, "pairwise_stats: group " + std::to_string(g) + " is empty");
+    if (ldy[g] < d) return op_fail(SVAE_EBADARG, "pairwise_stats: ldy below d in group " + std::to_string(g));
+  }
+  for (int l = 0; l < n_bw; ++l)
+    if (!(inv_two_sigma2[l] > 0.0) || !std::isfinite(inv_two_sigma2[l]))
+      return op_fail(SVAE_EBADARG, "pairwise_stats: bandwidth " + std::to_string(l) + " is not positive and finite");
+  if (self_group >= n_groups) return op_fail(SVAE_EBADARG, "pairwise_stats: self_group names no group");
+  if (self_group >= 0 && (n != m[self_group] || x != y[self_group]))
+    return op_fail(SVAE_EBADARG, "pairwise_stats: self_group needs x == y[self_group] and n == m[self_group]");
+  if (d > 2147483647LL || !pairwise_shape_ok(n, m, n_groups, n_bw))
+    return op_fail(SVAE_EBADCONFIG, "pairwise_stats: d above 2^31 - 1, or too many row or column tiles");
+  if (!scratch) return op_fail(SVAE_EBADARG, "pairwise_stats: null scratch");
+  pairwise_stats(x, n, ldx, y, m, ldy, n_groups, (int)d, self_group < 0 ? -1 : self_group, inv_two_sigma2, n_bw, ksum,
+                 nn_d2, (long long*)nn_idx, scratch, (hipStream_t)stream);
+  return op_done();
+}
+
+}  // extern "C"

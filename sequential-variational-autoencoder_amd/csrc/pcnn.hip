@@ -11,10 +11,9 @@
 #include "common.h"
 #include "knobs.h"
 #include "kernels.h"
+#include "opentry.h"
 #include "svae_hip.h"
 #include "svae_pcnn.h"
-
-void svae_tls_error(const std::string& msg);  // engine.cpp: svae_last_error(NULL)
 
 namespace {
 
@@ -2876,8 +2875,6 @@ int svae_pcnn_mask_edge(float* x, int n, int ho, int wo, int c, int ldx, int mas
                      wo, c, ldx, mask_edge);
   return hipchk();
 }
-
-static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 static int pcnn_nonlin(const float* x, int64_t rows, int c, int ldx, int kind, const float* mask, float keep,
                        uint64_t seed, void* y, int ldy, int y_bf16, float* h16_scale, void* stream) {

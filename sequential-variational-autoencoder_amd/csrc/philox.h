@@ -4,6 +4,17 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+// Counter word c2 of every draw made for a batch under one (seed, offset): the stream.  Two draws of a batch are
+// independent because they differ here, so a new per-batch draw takes the next number and no number is reused.
+enum PhiloxStream : unsigned {
+  PHILOX_NORMALS = 0,  // corrupt.h: the Gaussian pixel noise
+  PHILOX_PEPPER = 1,   // corrupt.h
+  PHILOX_SALT = 2,     // corrupt.h
+  PHILOX_DEGRADE = 3,  // degrade.hip: gates, sigma and boxes per image
+  PHILOX_CROPS = 4,    // crops.hip: image, scale, symmetry and origin per row
+  PHILOX_JPEG = 5,     // jpeg.hip: gate and quality per image
+};
+
 __device__ __forceinline__ void philox(unsigned& c0, unsigned& c1, unsigned& c2, unsigned& c3, unsigned k0,
                                        unsigned k1) {
 #pragma unroll
@@ -17,6 +28,15 @@ __device__ __forceinline__ void philox(unsigned& c0, unsigned& c1, unsigned& c2,
     k0 += 0x9E3779B9u;
     k1 += 0xBB67AE85u;
   }
+}
+
+// the four words of a per-image draw: counter (offset + b in c0 / c1, c2 = stream, c3 = block) under the key
+// (lo32(seed), hi32(seed))
+__device__ __forceinline__ void philox_image(unsigned long long seed, unsigned long long offset, long long b,
+                                             PhiloxStream stream, unsigned block, unsigned w[4]) {
+  const unsigned long long ctr = offset + (unsigned long long)b;
+  w[0] = (unsigned)ctr; w[1] = (unsigned)(ctr >> 32); w[2] = stream; w[3] = block;
+  philox(w[0], w[1], w[2], w[3], (unsigned)seed, (unsigned)(seed >> 32));
 }
 
 // four N(0,1) from the four words of one Philox output: u = (w + 0.5) 2^-32 in fp32, Box-Muller on words

@@ -25,14 +25,14 @@
 // LDS: max(h (w | 1), h wu + wu n_bins) + 2 h wu + 3 (h + w) doubles (+ 16 bytes): 69 KB at 64 x 64 with 33 bins
 // (two blocks per CU), 151 KB at SVAE_SPECTRUM_MAX_DIM square; all of it dynamic, the attribute is set once per
 // device.
+// svae_op_power_spectrum, with its argument checks, ends the file.
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
 #include <mutex>
 
 #include "common.h"
-#include "kernels.h"
-#include "svae_hip.h"
+#include "opentry.h"
 
 #pragma clang fp contract(off)
 
@@ -257,12 +257,8 @@ int ps_device() {
   return d >= 0 && d < 64 ? d : 0;
 }
 
-}  // namespace
-
-hipError_t power_spectrum(const float* x, int n, const float* y, int ny, int h, int w, int c, const double* win_y,
-                          const double* win_x, const double* tw_y, const double* tw_x, const int* bin, int n_bins,
-                          double* out, long long* nonfinite, hipStream_t s) {
-  // the attribute is per device: set once each, by whichever host thread comes first, and its result kept
+// the dynamic-LDS attribute is per device: set once each, by whichever host thread comes first, and its result kept
+hipError_t ps_lds_attribute() {
   static std::once_flag once[64];
   static hipError_t attr[64];
   const int dev = ps_device();
@@ -271,9 +267,34 @@ hipError_t power_spectrum(const float* x, int n, const float* y, int ny, int h, 
         (const void*)power_spectrum_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
         (int)ps_lds_bytes(SVAE_SPECTRUM_MAX_DIM, SVAE_SPECTRUM_MAX_DIM, SVAE_SPECTRUM_MAX_BINS));
   });
-  if (attr[dev] != hipSuccess) return attr[dev];
-  PsArgs a{x, y, ny, h, w, c, win_y, win_x, tw_y, tw_x, bin, n_bins, out, nonfinite};
-  hipLaunchKernelGGL(power_spectrum_kernel, dim3((unsigned)n * (unsigned)c), dim3(PS_THREADS), ps_lds_bytes(h, w, n_bins),
-                     s, a);
-  return hipGetLastError();
+  return attr[dev];
 }
+
+}  // namespace
+
+extern "C" {
+
+int svae_op_power_spectrum(const float* x, int n, const float* y, int ny, int h, int w, int c, const double* win_y,
+                           const double* win_x, const double* tw_y, const double* tw_x, const int32_t* bin, int n_bins,
+                           double* out, int64_t* nonfinite, void* stream) {
+  if (!x || !win_y || !win_x || !tw_y || !tw_x || !bin || !out)
+    return op_fail(SVAE_EBADARG, "power_spectrum: null pointer");
+  if (n <= 0 || ny <= 0 || c <= 0 || n_bins <= 0)
+    return op_fail(SVAE_EBADARG, "power_spectrum: n, ny, c and n_bins must be positive");
+  if (h < 2 || w < 2) return op_fail(SVAE_EBADARG, "power_spectrum: h and w must be at least 2");
+  if (y && n % ny != 0) return op_fail(SVAE_EBADARG, "power_spectrum: n must be a multiple of ny");
+  if (h > SVAE_SPECTRUM_MAX_DIM || w > SVAE_SPECTRUM_MAX_DIM || n_bins > SVAE_SPECTRUM_MAX_BINS)
+    return op_fail(SVAE_EBADCONFIG, "power_spectrum: at most " + std::to_string(SVAE_SPECTRUM_MAX_DIM) +
+                                        " rows and columns and " + std::to_string(SVAE_SPECTRUM_MAX_BINS) +
+                                        " bins");
+  if ((int64_t)h * w * c > 2147483647LL || (int64_t)n * c > 2147483647LL)
+    return op_fail(SVAE_EBADCONFIG, "power_spectrum: h * w * c or n * c above 2^31 - 1");
+  const hipError_t e = ps_lds_attribute();
+  if (e != hipSuccess) return op_fail(SVAE_EHIP, hipGetErrorString(e));
+  PsArgs a{x, y, ny, h, w, c, win_y, win_x, tw_y, tw_x, bin, n_bins, out, (long long*)nonfinite};
+  hipLaunchKernelGGL(power_spectrum_kernel, dim3((unsigned)n * (unsigned)c), dim3(PS_THREADS), ps_lds_bytes(h, w, n_bins),
+                     (hipStream_t)stream, a);
+  return op_done();
+}
+
+}  // extern "C"

@@ -12,12 +12,12 @@
 // the four waves in order, one partial row per chunk; stats_finish_kernel adds a segment's rows in chunk order.
 // A full group is one 16-byte load when x is 16-byte aligned (the Vec instance) and four 4-byte loads otherwise:
 // the same values into the same accumulators.
+// svae_op_stats_plan and svae_op_tensor_stats, with their argument checks, end the file.
 #include <cfloat>
 #include <cstdint>
 
 #include "common.h"
-#include "kernels.h"
-#include "svae_hip.h"
+#include "opentry.h"
 
 namespace {
 
@@ -161,7 +161,10 @@ __global__ __launch_bounds__(ST_THREADS) void stats_finish_kernel(const long lon
   out[s * 8 + q] = r;
 }
 
-}  // namespace
+// plan table (int64 words): [0, n_seg] the index of every segment's first chunk (entry n_seg = n_chunks), then
+// per chunk (begin, segment << 32 | length).  stats_plan returns the chunk count (table == nullptr: count only),
+// -1 for a negative, unordered or overlapping segment, -2 when cap_words < stats_plan_words().
+inline long long stats_plan_words(int n_seg, long long n_chunks) { return (long long)n_seg + 1 + 2 * n_chunks; }
 
 long long stats_plan(const long long* offsets, const long long* lengths, int n_seg, long long* table,
                      long long cap_words) {
@@ -193,6 +196,7 @@ long long stats_plan(const long long* offsets, const long long* lengths, int n_s
   return k;
 }
 
+// part: n_chunks * 8 doubles; out: n_seg * 8 doubles; at most two launches on s
 void tensor_stats(const float* x, const long long* plan, int n_seg, long long n_chunks, float c, double* part,
                   double* out, hipStream_t s) {
   if (n_seg <= 0) return;
@@ -200,7 +204,7 @@ void tensor_stats(const float* x, const long long* plan, int n_seg, long long n_
     const long long cap = 65536;  // grid-stride beyond this many blocks
     const dim3 grid((unsigned)(n_chunks < cap ? n_chunks : cap));
     const long long* chunks = plan + n_seg + 1;
-    if ((reinterpret_cast<uintptr_t>(x) & 15) == 0)
+    if (al16(x))
       hipLaunchKernelGGL(stats_chunk_kernel<true>, grid, dim3(ST_THREADS), 0, s, x, chunks, n_chunks, c, part);
     else
       hipLaunchKernelGGL(stats_chunk_kernel<false>, grid, dim3(ST_THREADS), 0, s, x, chunks, n_chunks, c, part);
@@ -209,3 +213,34 @@ void tensor_stats(const float* x, const long long* plan, int n_seg, long long n_
   hipLaunchKernelGGL(stats_finish_kernel, dim3((unsigned)((nt + ST_THREADS - 1) / ST_THREADS)), dim3(ST_THREADS), 0,
                      s, plan, part, n_seg, out);
 }
+
+}  // namespace
+
+extern "C" {
+
+int64_t svae_op_stats_plan(const int64_t* offsets, const int64_t* lengths, int32_t n_seg, int64_t* table,
+                           int64_t cap_words) {
+  if (n_seg < 0 || (n_seg > 0 && (!offsets || !lengths)) || cap_words < 0)
+    return op_fail(SVAE_EBADARG, "stats_plan: null segments or a negative count");
+  const long long n = stats_plan((const long long*)offsets, (const long long*)lengths, n_seg, (long long*)table,
+                                 cap_words);
+  if (n == -1)
+    return op_fail(SVAE_EBADARG, "stats_plan: segments must be non-negative, ascending and disjoint");
+  if (n == -2) {
+    const long long nc = stats_plan((const long long*)offsets, (const long long*)lengths, n_seg, nullptr, 0);
+    return op_fail(SVAE_EBADARG, "stats_plan: the table holds " + std::to_string((long long)cap_words) +
+                                     " words, the plan needs " + std::to_string(stats_plan_words(n_seg, nc)));
+  }
+  return n;
+}
+
+int svae_op_tensor_stats(const float* x, const int64_t* plan, int32_t n_seg, int64_t n_chunks, float c,
+                         double* partials, double* out, void* stream) {
+  if (!x || !plan || !partials || !out) return op_fail(SVAE_EBADARG, "tensor_stats: null pointer");
+  if (n_seg < 0 || n_chunks < 0) return op_fail(SVAE_EBADARG, "tensor_stats: negative count");
+  if (!(c >= 0.f)) return op_fail(SVAE_EBADARG, "tensor_stats: the clamp must be >= 0 (+inf: none)");
+  tensor_stats(x, (const long long*)plan, n_seg, n_chunks, c, partials, out, (hipStream_t)stream);
+  return op_done();
+}
+
+}  // extern "C"

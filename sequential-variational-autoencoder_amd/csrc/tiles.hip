@@ -7,10 +7,13 @@
 // gathers along the contiguous x * c run of an image row, of which a tile row is a contiguous piece: lanes run
 // along it, a block derives (image, row band) once, and no result depends on the launch geometry or on which
 // accesses the alignment lets be 16 bytes wide (the same values enter the same operations in the same order).
+// The dequantisation is pixel.h's; the two entry points, with their argument checks, end the file.
+#include <algorithm>
 #include <cstdint>
 
 #include "common.h"
-#include "kernels.h"
+#include "opentry.h"
+#include "pixel.h"
 
 namespace {
 
@@ -19,12 +22,26 @@ constexpr int TL_BAND = 8;          // output rows of one blend block, halved wh
 constexpr long long TL_MIN_ITEMS = 1024;  // (four blocks per CU: 24.5 us against 38.9 at bands of 8)
 constexpr int TL_UNITS = 1024;      // extract: 16-byte units (scalar path: elements) of one block
 
-// lo + q * qscale with the product and the sum each rounded to fp32 (batch.hip's mb_dequant)
-__device__ __forceinline__ float tl_dequant(unsigned char q, float lo, float qscale) {
-#pragma clang fp contract(off)
-  const float p = (float)q * qscale;
-  return lo + p;
-}
+// per axis: k = ceil((L - t) / s) + 1 tiles, tile i at min(i s, L - t); tile id (m ky + i) kx + j
+struct TileGeom {
+  int nimg, H, W, c, th, tw, sy, sx;
+  int ky, kx;                        // tiles per axis
+  long long n_tiles;                 // nimg * ky * kx
+};
+struct ExtractTilesArgs {
+  TileGeom g;
+  const void* images; int data_u8;
+  float lo, qscale;                  // qscale = (hi - lo) / 255 rounded to fp32 (make_batch's)
+  long long first, count;
+  float* tiles;
+};
+struct BlendTilesArgs {
+  TileGeom g;
+  const float* tiles; int nstack; long long stack_stride;
+  const void* source; int source_u8; const unsigned char* known;   // source and known: both or neither
+  float lo, qscale, qinv;            // qinv = 255 / (hi - lo) rounded to fp32
+  float* out; unsigned char* out_u8; // either may be nullptr
+};
 
 // (uint8) min(max(rintf((v - lo) * qinv), 0), 255): the difference and the product each rounded to fp32
 __device__ __forceinline__ unsigned tl_quant(float v, float lo, float qinv) {
@@ -84,10 +101,9 @@ __global__ __launch_bounds__(TL_THREADS) void extract_tiles_kernel(ExtractTilesA
             w = *reinterpret_cast<const unsigned*>(sp);
           else
             w = (unsigned)sp[0] | ((unsigned)sp[1] << 8) | ((unsigned)sp[2] << 16) | ((unsigned)sp[3] << 24);
-          v = make_float4(tl_dequant((unsigned char)(w & 0xFF), a.lo, a.qscale),
-                          tl_dequant((unsigned char)((w >> 8) & 0xFF), a.lo, a.qscale),
-                          tl_dequant((unsigned char)((w >> 16) & 0xFF), a.lo, a.qscale),
-                          tl_dequant((unsigned char)(w >> 24), a.lo, a.qscale));
+          float t[4];
+          u8_dequant4(w, a.lo, a.qscale, t);
+          v = make_float4(t[0], t[1], t[2], t[3]);
         } else {
           const float* sp = (const float*)a.images + s;
           if ((reinterpret_cast<uintptr_t>(sp) & 15) == 0)
@@ -97,7 +113,7 @@ __global__ __launch_bounds__(TL_THREADS) void extract_tiles_kernel(ExtractTilesA
         }
         *reinterpret_cast<float4*>(d) = v;
       } else {
-        *d = U8 ? tl_dequant(((const unsigned char*)a.images)[s], a.lo, a.qscale) : ((const float*)a.images)[s];
+        *d = U8 ? u8_dequant(((const unsigned char*)a.images)[s], a.lo, a.qscale) : ((const float*)a.images)[s];
       }
       q += dq;
       p += dp;
@@ -190,7 +206,7 @@ __global__ __launch_bounds__(TL_THREADS) void blend_tiles_kernel(BlendTilesArgs 
         v[q] = (float)(acc[q] / (double)(wy_sum * wsum[q]));
         if (q < cnt && a.known && a.known[(m * g.H + y) * g.W + x[q]]) {
           const long long s = (m * g.H + y) * (long long)n + e0 + q;
-          v[q] = a.source_u8 ? tl_dequant(((const unsigned char*)a.source)[s], a.lo, a.qscale)
+          v[q] = a.source_u8 ? u8_dequant(((const unsigned char*)a.source)[s], a.lo, a.qscale)
                              : ((const float*)a.source)[s];
         }
         if (a.out_u8) bytes |= tl_quant(v[q], a.lo, a.qinv) << (8 * q);
@@ -218,21 +234,73 @@ __global__ __launch_bounds__(TL_THREADS) void blend_tiles_kernel(BlendTilesArgs 
   }
 }
 
-inline bool al(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 constexpr long long TL_GRID_CAP = 1 << 20;  // grid-stride beyond this many blocks
+
+int tile_count(int L, int t, int s) { return (int)(((int64_t)L - t + s - 1) / s) + 1; }
+
+// the largest sum of window weights w1(p) = min(p + 1, t - p) over the tiles covering one position of an axis
+// (exact = false: an upper bound in O(1): at most ceil(t / s) + 1 tiles cover a position, each with at most ceil(t / 2))
+int64_t tile_axis_weight(int L, int t, int s, bool exact) {
+  const int k = tile_count(L, t, s);
+  if (!exact) return std::min<int64_t>(k, ((int64_t)t + s - 1) / s + 1) * (((int64_t)t + 1) / 2);
+  int64_t best = 0;
+  for (int64_t x = 0; x < L; ++x) {
+    int64_t hi = x >= (int64_t)L - t ? k - 1 : x / s, lo = x < t ? 0 : (x - t) / s + 1, sum = 0;
+    if (lo > k - 1) lo = k - 1;
+    for (int64_t i = lo; i <= hi; ++i) {
+      const int64_t p = x - std::min<int64_t>(i * s, (int64_t)L - t);
+      sum += std::min<int64_t>(p + 1, t - p);
+    }
+    best = std::max(best, sum);
+  }
+  return best;
+}
+
+// the checks the two tile ops share; fills g.  0, or the code op_fail() returned
+int tile_geometry(const char* op, int nimg, int H, int W, int c, int th, int tw, int sy, int sx, TileGeom& g) {
+  const std::string who(op);
+  if (nimg <= 0 || H <= 0 || W <= 0 || c <= 0 || th <= 0 || tw <= 0 || sy <= 0 || sx <= 0)
+    return op_fail(SVAE_EBADARG, who + ": nimg, H, W, c, th, tw, sy and sx must be positive");
+  if (th > H || tw > W) return op_fail(SVAE_EBADARG, who + ": the tile exceeds the image");
+  if (sy > th || sx > tw) return op_fail(SVAE_EBADARG, who + ": the stride exceeds the tile");
+  g.nimg = nimg; g.H = H; g.W = W; g.c = c; g.th = th; g.tw = tw; g.sy = sy; g.sx = sx;
+  g.ky = tile_count(H, th, sy); g.kx = tile_count(W, tw, sx);
+  g.n_tiles = (long long)nimg * g.ky * g.kx;
+  return 0;
+}
+
+int tile_sizes(const char* op, const TileGeom& g) {
+  if ((int64_t)g.th * g.tw * g.c > 2147483647LL || (int64_t)g.H * g.W * g.c > 2147483647LL)
+    return op_fail(SVAE_EBADCONFIG, std::string(op) + ": at most 2^31 - 1 elements per tile and per image");
+  return 0;
+}
 
 }  // namespace
 
-void extract_tiles(const ExtractTilesArgs& a, hipStream_t s) {
+extern "C" {
+
+int svae_op_extract_tiles(const void* images, int data_u8, int nimg, int H, int W, int c, int th, int tw, int sy,
+                          int sx, float lo, float hi, int64_t first, int64_t count, float* tiles, void* stream) {
+  if (!images || !tiles) return op_fail(SVAE_EBADARG, "extract_tiles: null images or tiles");
+  ExtractTilesArgs a{};
+  if (int rc = tile_geometry("extract_tiles", nimg, H, W, c, th, tw, sy, sx, a.g)) return rc;
+  if (count <= 0) return op_fail(SVAE_EBADARG, "extract_tiles: count must be positive");
+  if (first < 0 || first >= a.g.n_tiles)
+    return op_fail(SVAE_EBADARG, "extract_tiles: first must be in [0, n_tiles)");
+  if (data_u8 && !(lo < hi)) return op_fail(SVAE_EBADARG, "extract_tiles: lo >= hi with uint8 images");
+  if (int rc = tile_sizes("extract_tiles", a.g)) return rc;
+  a.images = images; a.data_u8 = data_u8 ? 1 : 0;
+  a.lo = lo; a.qscale = quant_scale(lo, hi).qscale;
+  a.first = first; a.count = count; a.tiles = tiles;
   const int n = a.g.tw * a.g.c;
-  const bool vec = n % 4 == 0 && al(a.tiles, 16);
+  const bool vec = n % 4 == 0 && al16(a.tiles);
   const int units = vec ? n / 4 : n;
   int band = (TL_UNITS + units - 1) / units;
   if (band > a.g.th) band = a.g.th;
   const int nbands = (a.g.th + band - 1) / band;
   const long long items = a.count * nbands;
   const dim3 grid((unsigned)(items < TL_GRID_CAP ? items : TL_GRID_CAP)), block(TL_THREADS);
+  hipStream_t s = (hipStream_t)stream;
   if (a.data_u8) {
     if (vec) hipLaunchKernelGGL((extract_tiles_kernel<true, true>), grid, block, 0, s, a, band, nbands);
     else hipLaunchKernelGGL((extract_tiles_kernel<true, false>), grid, block, 0, s, a, band, nbands);
@@ -240,15 +308,40 @@ void extract_tiles(const ExtractTilesArgs& a, hipStream_t s) {
     if (vec) hipLaunchKernelGGL((extract_tiles_kernel<false, true>), grid, block, 0, s, a, band, nbands);
     else hipLaunchKernelGGL((extract_tiles_kernel<false, false>), grid, block, 0, s, a, band, nbands);
   }
+  return op_done();
 }
 
-void blend_tiles(const BlendTilesArgs& a, hipStream_t s) {
+int svae_op_blend_tiles(const float* tiles, int nstack, int64_t stack_stride, int nimg, int H, int W, int c, int th,
+                        int tw, int sy, int sx, const void* source, int source_u8, const uint8_t* known, float lo,
+                        float hi, float* out, uint8_t* out_u8, void* stream) {
+  if (!tiles) return op_fail(SVAE_EBADARG, "blend_tiles: null tiles");
+  if (!out && !out_u8) return op_fail(SVAE_EBADARG, "blend_tiles: out and out_u8 are both null");
+  if ((known != nullptr) != (source != nullptr))
+    return op_fail(SVAE_EBADARG, "blend_tiles: known and source come together");
+  BlendTilesArgs a{};
+  if (int rc = tile_geometry("blend_tiles", nimg, H, W, c, th, tw, sy, sx, a.g)) return rc;
+  if (nstack <= 0) return op_fail(SVAE_EBADARG, "blend_tiles: nstack must be positive");
+  if (stack_stride < 0 || (unsigned __int128)stack_stride < (unsigned __int128)a.g.n_tiles * th * tw * c)
+    return op_fail(SVAE_EBADARG, "blend_tiles: stack_stride is smaller than a set of tiles");
+  if ((out_u8 || (source && source_u8)) && !(lo < hi))
+    return op_fail(SVAE_EBADARG, "blend_tiles: lo >= hi with a uint8 source or output");
+  if (int rc = tile_sizes("blend_tiles", a.g)) return rc;
+  const auto reaches = [&](bool exact) {  // both factors < 2^31 * 2^30: the comparison is made in fp64
+    return (double)tile_axis_weight(H, th, sy, exact) * (double)tile_axis_weight(W, tw, sx, exact) >= 536870912.0;
+  };
+  if (reaches(false) && reaches(true))
+    return op_fail(SVAE_EBADCONFIG, "blend_tiles: the weight sum of a pixel reaches 2^29");
+  a.tiles = tiles; a.nstack = nstack; a.stack_stride = stack_stride;
+  a.source = source; a.source_u8 = source_u8 ? 1 : 0; a.known = known;
+  const QScale q = quant_scale(lo, hi);
+  a.lo = lo; a.qscale = q.qscale; a.qinv = q.qinv;
+  a.out = out; a.out_u8 = out_u8;
   const long long n = (long long)a.g.W * a.g.c;
   const int tn = a.g.tw * a.g.c;
   BlendFlags f;
-  f.vec_in = al(a.tiles, 16) && a.stack_stride % 4 == 0 && tn % 4 == 0;
-  f.vec_out = a.out && al(a.out, 16) && n % 4 == 0;
-  f.vec_out8 = a.out_u8 && al(a.out_u8, 4) && n % 4 == 0;
+  f.vec_in = al16(a.tiles) && a.stack_stride % 4 == 0 && tn % 4 == 0;
+  f.vec_out = a.out && al16(a.out) && n % 4 == 0;
+  f.vec_out8 = a.out_u8 && (reinterpret_cast<uintptr_t>(a.out_u8) & 3) == 0 && n % 4 == 0;
   const int nchunks = (int)((n + 4 * TL_THREADS - 1) / (4 * TL_THREADS));
   int band = TL_BAND, nbands;
   long long items;
@@ -258,5 +351,8 @@ void blend_tiles(const BlendTilesArgs& a, hipStream_t s) {
     if (band == 1 || items >= TL_MIN_ITEMS) break;
   }
   const dim3 grid((unsigned)(items < TL_GRID_CAP ? items : TL_GRID_CAP)), block(TL_THREADS);
-  hipLaunchKernelGGL(blend_tiles_kernel, grid, block, 0, s, a, f, band, nbands, nchunks);
+  hipLaunchKernelGGL(blend_tiles_kernel, grid, block, 0, (hipStream_t)stream, a, f, band, nbands, nchunks);
+  return op_done();
 }
+
+}  // extern "C"
