@@ -374,6 +374,94 @@ int svae_op_splitfc(const float* z, int ldz, int zoff, int b, int k, const float
 int svae_op_splitfc_bwd(const float* z, int ldz, int zoff, int b, int k, const float* w, const float* beta, int j,
                         int f, int ldo, int64_t o_n, const float* mean, const float* invstd, const float* dout,
                         float* dw, float* dbeta, float* dz, void* scratch, int64_t scratch_bytes, void* stream);
+/* ---- the output tail of a chain step (csrc/misc.hip) and the chain-variant kernels (csrc/chain.hip), each group
+ * of launches the engine always issues together through the engine's own launchers.  Device pointers, the caller's
+ * stream and scratch, no allocation, no synchronisation.  SVAE_EBADARG (message prefixed by the op's name): a null
+ * pointer that the entry does not allow, a non-positive size, or what the entry says below. ---- */
+/* kernel family of a small-N gather launch, reported as variant[0]; variant[1] = lanes per pixel (LP; 0 for the
+ * plain kernel) */
+enum { SVAE_GCONV_PLAIN = 0, SVAE_GCONV_LP = 1, SVAE_GCONV_S2T = 2 };
+/* pure host: the family and LP of a 4x4 small-N gather with k gathered channels at pitch lda, nout <= 4 outputs and
+ * ho x wo output pixels per image; transpose != 0: the conv-T gather (the output layer and, with the roles of the
+ * tensors exchanged, the input gradient svae_op_conv_dgrad runs for a conv layer with cin % 4 != 0: k = lda = cout,
+ * nout = cin, ho = wo = h) */
+int svae_op_gconv_variant(int k, int lda, int nout, int transpose, int stride, int ho, int wo, int32_t* variant);
+/* family and LP of the last small-N gather launch of this process, as the launcher itself recorded it (-1, -1
+ * before the first; pure host; a test entry point, one caller at a time, like svae_op_wgrad_last_kernel) */
+int svae_op_gconv_last_kernel(int32_t* variant);
+/* The small-N gather as it is: c [n,ho,wo,n0+n1] (+)= bias + the 4x4 conv (transpose = 0) or conv-T of
+ * a [n,hi,wi,k] with w0 [16][n0][k] for columns 0 .. n0-1 and, when n1 > 0, w1 [16][n1][k] for the columns behind
+ * them (the launcher's dual-pointer form); bias0 [n0] and bias1 [n1] may be NULL; accumulate != 0 adds into c.
+ * k <= 256, n0 + n1 <= 4, stride 1|2; variant (two ints, may be NULL) reports the launch. */
+int svae_op_gconv_smalln(const float* a, int n, int hi, int wi, int k, const float* w0, int n0, const float* w1, int n1,
+                         const float* bias0, const float* bias1, int transpose, int stride, int accumulate, float* c,
+                         int32_t* variant, void* stream);
+/* The packed [C | ratio] output conv-T of a step: pack_out of w_out [4,4,c,f1], w_ratio [4,4,1,f1], b_out [c],
+ * b_ratio [1] (w_ratio and b_ratio both NULL: step 0, the ratio row and its bias packed as zeros) into wpack
+ * (16*(c+1)*f1 + 4 floats: [tap][c+1][f1] weights, then the 4 bias floats) and, in modes 1 and 2, its bf16 copy
+ * wpack_h (mode 1: 16*(c+1)*f1 bf16; mode 2: three such planes, plane q = bf16(w - the earlier planes)); then the
+ * stride-2 conv-T of x [n,hs,hs,f1] into a_out [n,2hs,2hs,c+1] through the engine's branch for the mode.
+ *   mode 0: the fp32 small-N gather; variant = (SVAE_GCONV_*, LP).  wpack_h may be NULL.
+ *   mode 1: the bf16 dispatch with the bias epilogue (x rounded to bf16 while staged); variant[0] =
+ *           SVAE_OUTCONVT_SMALLN_BF16 or the bf16 GEMM instance id (svae_kernel_name), variant[1] = 0.
+ *   mode 2: the split mode on the three planes where a split kernel takes the shape (variant as in mode 1), else
+ *           the fp32 gather-GEMM on wpack (SVAE_OUTCONVT_FP32_GEMM), as the engine falls back.
+ * f1 <= 256, and f1 % 4 == 0 in modes 1 and 2; x, wpack, wpack_h, a_out 16-byte aligned when f1 % 4 == 0.
+ * scratch (optional, 16-byte aligned): split-K slabs of the bf16 dispatch. */
+enum { SVAE_OUTCONVT_SMALLN_BF16 = 100, SVAE_OUTCONVT_FP32_GEMM = 101 };
+int svae_op_output_convt(const float* x, int n, int hs, int f1, const float* w_out, const float* w_ratio,
+                         const float* b_out, const float* b_ratio, int c, int mode, float* wpack, void* wpack_h,
+                         float* a_out, void* scratch, int64_t scratch_bytes, int32_t* variant, void* stream);
+/* output_fwd + loss_reduce on a [b,h,w,c+1]: out = (hi - lo) sigmoid(a[..c]) + lo; with xprev (may be NULL: step 0),
+ * r = minh + (maxh - minh) sigmoid(a[c]) and xhat = r out + (1 - r) xprev, else xhat = out.  rec_part
+ * [b][ceil(h w / 256)] (scratch and output: the per-block sums of (xhat - target)^2), rec_img [b] = the image's
+ * mean squared error, stats [2] = (mean_b rec_img, mean_b kl_img).  c in [1, 4]; c = 3 reads a in 16-byte rows. */
+int svae_op_output_fwd(const float* a, int b, int h, int w, int c, const float* xprev, const float* target, float lo,
+                       float hi, float minh, float maxh, const float* kl_img, float* xhat, float* rec_part,
+                       float* rec_img, float* stats, void* stream);
+/* output_bwd + colsum_small: g = (dxhat_in ? dxhat_in : 0) + 2 rec_coef (xhat - target); da [b,h,w,c+1] = the
+ * gradient of the pre-activations (ratio column 0 without xprev), dxprev = (1 - r) g (written only with xprev, then
+ * required), db_out [c] and db_ratio [1] (may be NULL: dropped) = the column sums of da.  scratch >= 1024 floats.
+ * c = 4 (outside any model): no bias sums, db_out and db_ratio NULL. */
+int svae_op_output_bwd(const float* a, int b, int h, int w, int c, const float* xprev, const float* xhat,
+                       const float* target, float lo, float hi, float minh, float maxh, float rec_coef,
+                       const float* dxhat_in, float* da, float* dxprev, float* db_out, float* db_ratio, void* scratch,
+                       int64_t scratch_bytes, void* stream);
+/* One layer of the stddev network on in [n,h,w] pixels of pitch ldi (in_sig != 0: the layer reads sigmoid(in), as
+ * layer 0 reads the output conv-T pre-activation at ldi = c + 1): pre = conv2d_same(in, wt [4,4,ci,co]) (stride 1,
+ * pad 1 before / 2 after), mean / invstd [co] over the n h w rows (biased variance, eps 1e-3), act = lrelu_0.1((pre
+ * - mean) invstd + beta).  ci, co <= 8; h % 4 == 0 (the limit of the layer's weight gradient, shared by both entry
+ * points); scratch >= ceil(n h w / 256) * 2 co doubles, 16-byte aligned. */
+int svae_op_sd_layer(const float* in, int ldi, int in_sig, int n, int h, int w, int ci, const float* wt, int co,
+                     const float* beta, float* pre, float* mean, float* invstd, float* act, void* scratch,
+                     int64_t scratch_bytes, void* stream);
+/* Its backward from dact [n,h,w,co] and the forward's pre, mean, invstd, beta: dpre [n,h,w,co], dbeta [co],
+ * dw [4,4,ci,co], and the input gradient: mode 0: din[q * ldd + i] = v; mode 1 (layer 0): din[q * ldd + i] +=
+ * v s (1 - s) with s = sigmoid(in[q * ldi + i]).  scratch (16-byte aligned) >= ceil(n h w / 256) * 2 co doubles
+ * rounded up to 16 bytes + 16 floats + n (h / 4) 16 ci co floats. */
+int svae_op_sd_layer_bwd(const float* dact, const float* pre, const float* mean, const float* invstd,
+                         const float* beta, const float* in, int ldi, int in_sig, int n, int h, int w, int ci,
+                         const float* wt, int co, int mode, float* dpre, float* dbeta, float* dw, float* din, int ldd,
+                         void* scratch, int64_t scratch_bytes, void* stream);
+/* The stddev head: sd [b,h,w] = smax sigmoid(act . w5 + b5) on act [b,h,w,ci]; sample = mle + reg sd noise
+ * ([b,h,w,c] each); rec_part [b][ceil(h w / 256)] = per-block sums of log sd + 0.5 log 2 pi + 0.5 ((mle - target) /
+ * sd)^2 over pixels and channels (the layout loss_reduce reads). */
+int svae_op_sd_head_fwd(const float* act, int ci, const float* w5, const float* b5, float smax, const float* mle,
+                        const float* target, const float* noise, float reg, int b, int h, int w, int c, float* sd,
+                        float* sample, float* rec_part, void* stream);
+/* Its backward for the loss sum(dsample * sample) + nll_coef * sum(NLL terms) (dsample may be NULL: zero): dmle
+ * [b,h,w,c], dact [b,h,w,ci], dw5 [ci], db5 [1].  scratch >= ceil(b h w / 256) * (ci + 1) floats. */
+int svae_op_sd_head_bwd(const float* act, int ci, const float* w5, const float* b5, float smax, const float* mle,
+                        const float* target, const float* noise, float reg, float nll_coef, const float* dsample, int b,
+                        int h, int w, int c, float* dmle, float* dact, float* dw5, float* db5, void* scratch,
+                        int64_t scratch_bytes, void* stream);
+/* sample = mle + scale * noise over n elements */
+int svae_op_chain_noise(const float* mle, const float* noise, float scale, int64_t n, float* sample, void* stream);
+/* out = (dxin ? dxin : 0) + 2 coef ((xp ? x - xp : 0) - (xn ? xn - x : 0)); dxin, xp, xn may be NULL; out may be dxin */
+int svae_op_imp_seed(const float* dxin, const float* xp, const float* x, const float* xn, float coef, int64_t n,
+                     float* out, void* stream);
+/* out[i] = sum over image i's per_img elements of (a - b)^2 */
+int svae_op_sqdiff_img(const float* a, const float* b, int nimg, int64_t per_img, float* out, void* stream);
 /* The training batch in one launch on `stream` (no allocation, no synchronisation): rows of a
  * device-resident dataset data [N, per_image] (uint8 when data_u8 = 1, else fp32) are gathered,
  * dequantised into the clean `target` and corrupted into the denoising `input`, both [n, per_image]

@@ -191,6 +191,24 @@ def _load(path):
                              vp], i32),
         "svae_op_splitfc_bwd": ([vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, i64,
                                  vp], i32),
+        "svae_op_gconv_variant": ([i32, i32, i32, i32, i32, i32, i32, ctypes.POINTER(i32)], i32),
+        "svae_op_gconv_last_kernel": ([ctypes.POINTER(i32)], i32),
+        "svae_op_gconv_smalln": ([vp, i32, i32, i32, i32, vp, i32, vp, i32, vp, vp, i32, i32, i32, vp,
+                                  ctypes.POINTER(i32), vp], i32),
+        "svae_op_output_convt": ([vp, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, i64,
+                                  ctypes.POINTER(i32), vp], i32),
+        "svae_op_output_fwd": ([vp, i32, i32, i32, i32, vp, vp, f32, f32, f32, f32, vp, vp, vp, vp, vp, vp], i32),
+        "svae_op_output_bwd": ([vp, i32, i32, i32, i32, vp, vp, vp, f32, f32, f32, f32, f32, vp, vp, vp, vp, vp, vp,
+                                i64, vp], i32),
+        "svae_op_sd_layer": ([vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, i64, vp], i32),
+        "svae_op_sd_layer_bwd": ([vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp,
+                                  i32, vp, i64, vp], i32),
+        "svae_op_sd_head_fwd": ([vp, i32, vp, vp, f32, vp, vp, vp, f32, i32, i32, i32, i32, vp, vp, vp, vp], i32),
+        "svae_op_sd_head_bwd": ([vp, i32, vp, vp, f32, vp, vp, vp, f32, f32, vp, i32, i32, i32, i32, vp, vp, vp, vp,
+                                 vp, i64, vp], i32),
+        "svae_op_chain_noise": ([vp, vp, f32, i64, vp, vp], i32),
+        "svae_op_imp_seed": ([vp, vp, vp, vp, f32, i64, vp, vp], i32),
+        "svae_op_sqdiff_img": ([vp, vp, i32, i64, vp, vp], i32),
         "svae_probe_begin": ([vp, i32, i32], i32),
         "svae_probe_end": ([vp, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(ctypes.c_double),
                             ctypes.POINTER(ctypes.c_double)], i32),
@@ -274,7 +292,11 @@ EXPORTED = ["svae_param_count", "svae_param_layout", "svae_create", "svae_destro
             "svae_op_dense_bf16", "svae_op_fc_wgrad", "svae_op_image_metrics",
             "svae_op_mixture_logdensity", "svae_op_pairwise_scratch_bytes", "svae_op_pairwise_stats",
             "svae_op_degrade_batch", "svae_op_extract_tiles", "svae_op_blend_tiles", "svae_op_crop_batch",
-            "svae_op_jpeg_batch", "svae_rng_offset", "svae_op_power_spectrum", "svae_set_ema", "svae_op_ema"]
+            "svae_op_jpeg_batch", "svae_rng_offset", "svae_op_power_spectrum", "svae_set_ema", "svae_op_ema",
+            "svae_op_gconv_variant", "svae_op_gconv_last_kernel", "svae_op_gconv_smalln", "svae_op_output_convt",
+            "svae_op_output_fwd", "svae_op_output_bwd",
+            "svae_op_sd_layer", "svae_op_sd_layer_bwd", "svae_op_sd_head_fwd", "svae_op_sd_head_bwd",
+            "svae_op_chain_noise", "svae_op_imp_seed", "svae_op_sqdiff_img"]
 # include/svae_pcnn.h (the PixelCNN++ head)
 PCNN_EXPORTED = ["svae_pcnn_wnorm", "svae_pcnn_wnorm_bwd", "svae_pcnn_conv", "svae_pcnn_conv_wgrad", "svae_pcnn_colsum",
                  "svae_pcnn_colsum_absmax", "svae_pcnn_im2col_h16", "svae_pcnn_conv_planes_amax",

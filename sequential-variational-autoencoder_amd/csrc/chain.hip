@@ -13,6 +13,7 @@
 // per-image losses) writes per-block partials that a second kernel sums in a fixed order, so
 // results are bit-deterministic.
 #include "kernels.h"
+#include "opentry.h"
 
 #define SD_TPB 256
 #define SD_MAXC 8
@@ -445,3 +446,121 @@ void imp_seed(const float* dxin, const float* xp, const float* x, const float* x
 void sqdiff_img(const float* a, const float* b, int B, long long per_img, float* out, hipStream_t s) {
   hipLaunchKernelGGL(sqdiff_img_kernel, dim3(B), dim3(SD_TPB), 0, s, a, b, per_img, out);
 }
+
+// ---- context-free entry points (kernel-level parity tests): each group of launches the engine issues together,
+// through the launchers above, on the caller's stream and scratch ----
+namespace {
+
+// the limits every stddev-network kernel shares: <= SD_MAXC channels, whole SD_ROWS-row weight-gradient blocks
+const char* sd_shape_error(int n, int h, int w, int ci, int co) {
+  if (n <= 0 || h <= 0 || w <= 0) return "n, h and w must be positive";
+  if (ci < 1 || ci > SD_MAXC || co < 1 || co > SD_MAXC) return "channels must be in [1, 8]";
+  if (h % SD_ROWS) return "h must be a multiple of 4 (the weight gradient covers h / 4 row blocks per image)";
+  return nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
+int svae_op_sd_layer(const float* in, int ldi, int in_sig, int n, int h, int w, int ci, const float* wt, int co,
+                     const float* beta, float* pre, float* mean, float* invstd, float* act, void* scratch,
+                     int64_t scratch_bytes, void* stream) {
+  if (!in || !wt || !beta || !pre || !mean || !invstd || !act || !scratch)
+    return op_fail(SVAE_EBADARG, "sd_layer: null pointer");
+  if (const char* e = sd_shape_error(n, h, w, ci, co)) return op_fail(SVAE_EBADARG, std::string("sd_layer: ") + e);
+  if (ldi < ci) return op_fail(SVAE_EBADARG, "sd_layer: ldi < ci");
+  const long long P = (long long)n * h * w;
+  const int nblk = sd_pixel_blocks(P);
+  if ((int64_t)nblk * 2 * co * (int64_t)sizeof(double) > scratch_bytes || !al16(scratch))
+    return op_fail(SVAE_EBADARG, "sd_layer: scratch too small or not 16-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  double* part = (double*)scratch;
+  sd_conv_fwd(in, ldi, in_sig != 0, ci, wt, co, h, w, P, pre, part, s);
+  sd_stat_fin(part, nblk, co, P, 1e-3f, 0, mean, invstd, nullptr, nullptr, s);
+  sd_bn_apply(pre, co, P, mean, invstd, beta, act, s);
+  return op_done();
+}
+
+int svae_op_sd_layer_bwd(const float* dact, const float* pre, const float* mean, const float* invstd,
+                         const float* beta, const float* in, int ldi, int in_sig, int n, int h, int w, int ci,
+                         const float* wt, int co, int mode, float* dpre, float* dbeta, float* dw, float* din, int ldd,
+                         void* scratch, int64_t scratch_bytes, void* stream) {
+  if (!dact || !pre || !mean || !invstd || !beta || !in || !wt || !dpre || !dbeta || !dw || !din || !scratch)
+    return op_fail(SVAE_EBADARG, "sd_layer_bwd: null pointer");
+  if (const char* e = sd_shape_error(n, h, w, ci, co)) return op_fail(SVAE_EBADARG, std::string("sd_layer_bwd: ") + e);
+  if (ldi < ci || ldd < ci || (mode != 0 && mode != 1)) return op_fail(SVAE_EBADARG, "sd_layer_bwd: ldi, ldd or mode");
+  const long long P = (long long)n * h * w;
+  const int nblk = sd_pixel_blocks(P);
+  // scratch: the fp64 block partials, the (S, Q) sums, the weight-gradient slabs
+  const int64_t b_part = ((int64_t)nblk * 2 * co * (int64_t)sizeof(double) + 15) / 16 * 16;
+  const int64_t b_sums = 2 * SD_MAXC * (int64_t)sizeof(float);
+  const int64_t b_wpart = (int64_t)sd_wgrad_blocks(n, h) * 16 * ci * co * (int64_t)sizeof(float);
+  if (b_part + b_sums + b_wpart > scratch_bytes || !al16(scratch))
+    return op_fail(SVAE_EBADARG, "sd_layer_bwd: scratch too small or not 16-byte aligned");
+  if (((int64_t)(SD_ROWS + 3) * (w + 3) * ci + (int64_t)SD_ROWS * w * co) * (int64_t)sizeof(float) > 65536)
+    return op_fail(SVAE_EBADARG, "sd_layer_bwd: the weight gradient's row window does not fit the LDS");
+  hipStream_t s = (hipStream_t)stream;
+  double* part = (double*)scratch;
+  float* sums = (float*)((char*)scratch + b_part);
+  float* wpart = sums + 2 * SD_MAXC;
+  sd_bn_bwd_reduce(dact, pre, co, P, mean, invstd, beta, part, s);
+  sd_stat_fin(part, nblk, co, P, 0.f, 1, nullptr, nullptr, sums, dbeta, s);
+  sd_bn_bwd_apply(dact, pre, co, P, mean, invstd, beta, sums, dpre, s);
+  sd_conv_wgrad(in, ldi, in_sig != 0, ci, dpre, co, n, h, w, wpart, dw, s);
+  if (mode == 0) sd_conv_dgrad(dpre, co, wt, ci, h, w, P, din, ldd, nullptr, 0, 0, s);
+  else sd_conv_dgrad(dpre, co, wt, ci, h, w, P, din, ldd, in, ldi, 1, s);
+  return op_done();
+}
+
+int svae_op_sd_head_fwd(const float* act, int ci, const float* w5, const float* b5, float smax, const float* mle,
+                        const float* target, const float* noise, float reg, int b, int h, int w, int c, float* sd,
+                        float* sample, float* rec_part, void* stream) {
+  if (!act || !w5 || !b5 || !mle || !target || !noise || !sd || !sample || !rec_part)
+    return op_fail(SVAE_EBADARG, "sd_head_fwd: null pointer");
+  if (b <= 0 || h <= 0 || w <= 0 || c <= 0 || ci < 1 || ci > SD_MAXC || !(smax > 0.f))
+    return op_fail(SVAE_EBADARG, "sd_head_fwd: sizes must be positive, ci in [1, 8], smax > 0");
+  sd_head_fwd(act, ci, w5, b5, smax, mle, target, noise, reg, b, c, h * w, sd, sample, rec_part,
+              output_blocks_per_img(h * w), (hipStream_t)stream);
+  return op_done();
+}
+
+int svae_op_sd_head_bwd(const float* act, int ci, const float* w5, const float* b5, float smax, const float* mle,
+                        const float* target, const float* noise, float reg, float nll_coef, const float* dsample, int b,
+                        int h, int w, int c, float* dmle, float* dact, float* dw5, float* db5, void* scratch,
+                        int64_t scratch_bytes, void* stream) {
+  if (!act || !w5 || !b5 || !mle || !target || !noise || !dmle || !dact || !dw5 || !db5 || !scratch)
+    return op_fail(SVAE_EBADARG, "sd_head_bwd: null pointer");
+  if (b <= 0 || h <= 0 || w <= 0 || c <= 0 || ci < 1 || ci > SD_MAXC || !(smax > 0.f))
+    return op_fail(SVAE_EBADARG, "sd_head_bwd: sizes must be positive, ci in [1, 8], smax > 0");
+  const long long P = (long long)b * h * w;
+  if ((int64_t)sd_pixel_blocks(P) * (ci + 1) * (int64_t)sizeof(float) > scratch_bytes)
+    return op_fail(SVAE_EBADARG, "sd_head_bwd: scratch too small");
+  sd_head_bwd(act, ci, w5, b5, smax, mle, target, noise, reg, nll_coef, dsample, c, P, dmle, dact, (float*)scratch, dw5,
+              db5, (hipStream_t)stream);
+  return op_done();
+}
+
+int svae_op_chain_noise(const float* mle, const float* noise, float scale, int64_t n, float* sample, void* stream) {
+  if (!mle || !noise || !sample) return op_fail(SVAE_EBADARG, "chain_noise: null pointer");
+  if (n <= 0) return op_fail(SVAE_EBADARG, "chain_noise: n must be positive");
+  chain_noise(mle, noise, scale, n, sample, (hipStream_t)stream);
+  return op_done();
+}
+
+int svae_op_imp_seed(const float* dxin, const float* xp, const float* x, const float* xn, float coef, int64_t n,
+                     float* out, void* stream) {
+  if (!x || !out) return op_fail(SVAE_EBADARG, "imp_seed: null pointer");
+  if (n <= 0) return op_fail(SVAE_EBADARG, "imp_seed: n must be positive");
+  imp_seed(dxin, xp, x, xn, coef, n, out, (hipStream_t)stream);
+  return op_done();
+}
+
+int svae_op_sqdiff_img(const float* a, const float* b, int nimg, int64_t per_img, float* out, void* stream) {
+  if (!a || !b || !out) return op_fail(SVAE_EBADARG, "sqdiff_img: null pointer");
+  if (nimg <= 0 || per_img <= 0) return op_fail(SVAE_EBADARG, "sqdiff_img: nimg and per_img must be positive");
+  sqdiff_img(a, b, nimg, per_img, out, (hipStream_t)stream);
+  return op_done();
+}
+
+}  // extern "C"

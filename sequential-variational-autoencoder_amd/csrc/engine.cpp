@@ -3478,6 +3478,88 @@ int svae_op_conv_dgrad(const float* dy, int n, int h, int cin, const float* w, i
   return op_done();
 }
 
+// The packed [C | ratio] output conv-T of a step as svae_forward issues it: pack_out, then the branch of `mode`
+static_assert(SVAE_OUTCONVT_SMALLN_BF16 > KID_COUNT && SVAE_OUTCONVT_FP32_GEMM > KID_COUNT,
+              "the output conv-T's own kernel codes lie above the bf16 GEMM instance ids");
+int svae_op_output_convt(const float* x, int n, int hs, int f1, const float* w_out, const float* w_ratio,
+                         const float* b_out, const float* b_ratio, int c, int mode, float* wpack, void* wpack_h,
+                         float* a_out, void* scratch, int64_t scratch_bytes, int32_t* variant, void* stream) {
+  if (!x || !w_out || !b_out || !wpack || !a_out || ((w_ratio != nullptr) != (b_ratio != nullptr)))
+    return fail(nullptr, SVAE_EBADARG, "output_convt: null pointer (w_ratio and b_ratio go together)");
+  if (n <= 0 || hs <= 0 || f1 <= 0 || c < 1 || c > 3)
+    return fail(nullptr, SVAE_EBADARG, "output_convt: n, hs, f1 must be positive and c in [1, 3]");
+  if (mode < 0 || mode > 2) return fail(nullptr, SVAE_EBADARG, "output_convt: mode must be 0 (fp32), 1 (bf16) or 2 (split)");
+  if (mode != 0 && (!wpack_h || f1 % 4)) return fail(nullptr, SVAE_EBADARG, "output_convt: modes 1 and 2 need wpack_h and f1 % 4 == 0");
+  if ((long long)n * 4 * hs * hs > 0x7fffffffLL || 16LL * 4 * f1 * (long long)sizeof(float) > 65536)
+    return fail(nullptr, SVAE_EBADARG, "output_convt: too many pixels, or a weight table that does not fit the LDS");
+  if (f1 % 4 == 0 && (((uintptr_t)x | (uintptr_t)wpack | (uintptr_t)wpack_h | (uintptr_t)a_out) & 15))
+    return fail(nullptr, SVAE_EBADARG, "output_convt: f1 % 4 == 0 reads x, wpack and wpack_h in 16-byte vectors");
+  if (scratch_bytes < 0 || (scratch && ((uintptr_t)scratch & 15))) return fail(nullptr, SVAE_EBADARG, "output_convt: scratch");
+  hipStream_t s = (hipStream_t)stream;
+  const int C1 = c + 1;
+  // pack_out addresses its four tensors as offsets >= 0 from one base: the lowest of the caller's pointers
+  const float* base = w_out;
+  if (b_out < base) base = b_out;
+  if (w_ratio && w_ratio < base) base = w_ratio;
+  if (b_ratio && b_ratio < base) base = b_ratio;
+  PackOutArgs pa{};
+  pa.P = base;
+  pa.C = c;
+  pa.F1 = f1;
+  pa.nsp = mode == 2 ? 3 : 1;
+  pa.owout[0] = w_out - base;
+  pa.obout[0] = b_out - base;
+  pa.owratio[0] = w_ratio ? w_ratio - base : -1;
+  pa.obratio[0] = b_ratio ? b_ratio - base : -1;
+  pa.wpack[0] = wpack;
+  pa.wpack_h[0] = mode != 0 ? (__bf16*)wpack_h : nullptr;
+  pack_out(pa, 1, s);
+  float* bpack = wpack + 16 * C1 * f1;
+  ConvGeom og{GM_CONVT, n, hs, hs, 2 * hs, 2 * hs, 2, 1, 4};
+  if (mode == 0) {  // one 4-wide small-N gather with the packed bias
+    gconv_smalln(x, f1, f1, wpack, C1, nullptr, 0, (long long)C1 * f1, 0, bpack, nullptr, og, (long long)n * 4 * hs * hs,
+                 a_out, C1, 0, s);
+    if (variant) {
+      int lp = 0;
+      variant[0] = gconv_smalln_path(f1, f1, C1, og, &lp);
+      variant[1] = lp;
+    }
+    return op_done();
+  }
+  static svae_ctx dummy;
+  dummy.m.g.B = n;
+  dummy.m.g.bf16 = 1;
+  dummy.m.g.split = mode == 2;
+  dummy.st = s;
+  dummy.slab = (float*)scratch;
+  dummy.slab_cap = scratch ? scratch_bytes / (int64_t)sizeof(float) : 0;
+  FwdArgs a{};  // as svae_forward builds it
+  a.A = x; a.lda = f1; a.a_bf16 = 0;
+  a.B = wpack;
+  a.Bh = wpack_h; a.b_nk = 1; a.ldb = f1; a.b_tap = (long long)C1 * f1;
+  a.b_plane = mode == 2 ? 16LL * C1 * f1 : 0;
+  a.C = a_out; a.ldc = C1;
+  a.N = C1; a.Cin = f1;
+  a.g = og;
+  a.rows = n * hs * hs; a.nclass = 4;
+  a.bias = bpack;
+  if (variant) {  // the choices of gemm() and igemm_bf16_path(), asked of the same host functions
+    FwdArgs q = a;
+    q.part = dummy.slab; q.part_cap = dummy.slab_cap;
+    if (mode == 2) q.nsp = 3;
+    variant[1] = 0;
+    if (mode == 2 && !igemm_split_ok(q, 1)) variant[0] = SVAE_OUTCONVT_FP32_GEMM;
+    else if (mode == 1 && smalln_ok(q)) variant[0] = SVAE_OUTCONVT_SMALLN_BF16;
+    else if (mode == 2 && halo_x3_plan(q, 1) <= 0 && halo_kw_plan(q, 1) <= 0) variant[0] = SVAE_OUTCONVT_SMALLN_BF16;
+    else variant[0] = igemm_bf16_kid(q);
+  }
+  const int r = gemm(&dummy, a, 1);
+  dummy.m.g.bf16 = 0;
+  dummy.m.g.split = 0;
+  if (r < 0) return fail(nullptr, SVAE_EBADARG, "output_convt: no kernel for this launch");
+  return op_done();
+}
+
 int svae_op_conv_wgrad(const float* x, int n, int h, int cin, const float* dy, int cout, int stride, int transpose,
                        float* dw, void* scratch, int64_t scratch_bytes, void* stream) {
   if (!x || !dy || !dw || !scratch) return fail(nullptr, SVAE_EBADARG, "bad op args");

@@ -1474,7 +1474,7 @@ static int pertap_plan(const FwdArgs& a, int groups, int* ksplit) {
   const int Ktot = ntap * a.Cin;
   const int nk = (a.Cin % BKB) ? (Ktot + BKB - 1) / BKB : ntap * (a.Cin / BKB);
   int ks = 1;
-  if (blocks < 512 && a.part) {
+  if (blocks < 512 && a.part && a.N % 4 == 0) {  // the split-K reduce works on column quads (as in halo_plan)
     ks = (int)std::min<long long>((768 + blocks - 1) / blocks, 8);
     ks = std::min(ks, nk / 4);  // keep >= 4 K steps per split
     const long long rows_total = (long long)a.rows * a.nclass;

@@ -282,6 +282,10 @@ void heads_bwd(const float* X, long long x_gs, float* dX, long long dx_gs, int B
 
 // ---- small-N gather conv (N <= 4: output conv-T 32->3(+1), encoder layer-0 dgrad) ----
 // C[p][o] (+)= bias + sum_tap sum_k A[src(p,tap)][k] * W(tap,o,k); W0 [tap][n0][K], W1 [tap][n1][K]
+// which kernel family a launch takes (= SVAE_GCONV_* of include/svae_hip.h) and, through *lp, its lanes per pixel
+// (0 for the plain kernel): N = n0 + n1 outputs
+enum { GCONV_PLAIN = 0, GCONV_LP = 1, GCONV_S2T = 2 };
+int gconv_smalln_path(int K, int lda, int N, const ConvGeom& g, int* lp);
 void gconv_smalln(const float* A, int lda, int K, const float* W0, int n0, const float* W1, int n1, long long w_tap,
                   long long w1_tap, const float* bias0, const float* bias1, ConvGeom g, long long rows_total,
                   float* C, int ldc, int accumulate, hipStream_t s);

@@ -8,6 +8,7 @@
 #include "knobs.h"
 #include "kernels.h"
 #include "philox.h"
+#include "opentry.h"
 
 #define KMAX 32  // max latent dims per level handled in registers (LSUN: 30)
 
@@ -1155,14 +1156,35 @@ __global__ __launch_bounds__(256) void gconv_s2t_kernel(const float* A, int lda,
   }
 }
 
+// family and lanes per pixel of the last gconv_smalln launch of this process (-1: none yet); test entry points, one
+// caller at a time, as svae_op_wgrad_last_kernel
+static int g_gconv_last[2] = {-1, -1};
+
+// the one rule that picks the kernel family and its lanes per pixel (gconv_smalln and svae_op_gconv_variant both ask it)
+int gconv_smalln_path(int K, int lda, int N, const ConvGeom& g, int* lp) {
+  if (g.mode == GM_CONVT && g.stride == 2 && g.ksz == 4 && (lda & 3) == 0 && N <= 4 &&
+      (K == 16 || K == 32 || K == 64) && g.Ho % 2 == 0 && g.Wo % 2 == 0) {
+    *lp = K / 4;
+    return GCONV_S2T;
+  }
+  if ((K & 3) == 0 && (lda & 3) == 0 && K >= 16 && K <= 256 && (K & (K - 1)) == 0 && g.ksz <= 4 && N <= 4) {
+    *lp = K / 4 > 64 ? 64 : K / 4;  // lanes per pixel (power of two)
+    return GCONV_LP;
+  }
+  *lp = 0;
+  return GCONV_PLAIN;
+}
+
 void gconv_smalln(const float* A, int lda, int K, const float* W0, int n0, const float* W1, int n1, long long w_tap,
                   long long w1_tap, const float* bias0, const float* bias1, ConvGeom g, long long rows_total,
                   float* C, int ldc, int accumulate, hipStream_t s) {
   size_t lds = (size_t)g.ksz * g.ksz * 4 * K * sizeof(float);
-  if (g.mode == GM_CONVT && g.stride == 2 && g.ksz == 4 && (lda & 3) == 0 && n0 + n1 <= 4 &&
-      (K == 16 || K == 32 || K == 64) && g.Ho % 2 == 0 && g.Wo % 2 == 0) {
+  int lp = 0;
+  const int family = gconv_smalln_path(K, lda, n0 + n1, g, &lp);
+  g_gconv_last[0] = family;  // what svae_op_gconv_last_kernel reports
+  g_gconv_last[1] = lp;
+  if (family == GCONV_S2T) {
     const long long pix = (long long)g.nimg * (g.Ho / 2) * (g.Wo / 2);
-    const int lp = K / 4;
     dim3 grid((unsigned)std::min<long long>((pix * lp + 255) / 256, 1024), 4);
     if (lp == 4)
       hipLaunchKernelGGL(gconv_s2t_kernel<4>, grid, dim3(256), 0, s, A, lda, K, W0, n0, W1, n1, w_tap, w1_tap, bias0,
@@ -1175,8 +1197,7 @@ void gconv_smalln(const float* A, int lda, int K, const float* W0, int n0, const
                          bias1, g, C, ldc, accumulate);
     return;
   }
-  if ((K & 3) == 0 && (lda & 3) == 0 && K >= 16 && K <= 256 && (K & (K - 1)) == 0 && g.ksz <= 4 && n0 + n1 <= 4) {
-    const int lp = K / 4 > 64 ? 64 : K / 4;  // lanes per pixel (power of two)
+  if (family == GCONV_LP) {
     const long long threads = rows_total * lp;
     dim3 grid((unsigned)std::min<long long>((threads + 255) / 256, 2048));
     if (lp == 4)
@@ -1581,3 +1602,88 @@ void pack_out(const PackOutArgs& a, int nt, hipStream_t s) {
   const int n = 16 * (a.C + 1) * a.F1 + 4;
   hipLaunchKernelGGL(pack_out_kernel, dim3((n + 255) / 256, nt), dim3(256), 0, s, a);
 }
+
+// ---- context-free entry points of the output tail (kernel-level parity tests): the launches every chain step ends
+// in, through the launchers above, on the caller's stream and scratch ----
+static_assert(SVAE_GCONV_PLAIN == GCONV_PLAIN && SVAE_GCONV_LP == GCONV_LP && SVAE_GCONV_S2T == GCONV_S2T,
+              "include/svae_hip.h and kernels.h name the small-N gather kernels alike");
+
+extern "C" {
+
+int svae_op_gconv_last_kernel(int32_t* variant) {
+  if (!variant) return op_fail(SVAE_EBADARG, "gconv_last_kernel: null pointer");
+  variant[0] = g_gconv_last[0];
+  variant[1] = g_gconv_last[1];
+  return 0;
+}
+
+// The small-N gather as it is: c[p][0..n0+n1) (+)= bias + conv / conv-T of a [n,hi,wi,k] (pitch k) with w0 [16][n0][k]
+// and, optionally, w1 [16][n1][k] for the columns behind n0 (the dual-pointer form)
+int svae_op_gconv_smalln(const float* a, int n, int hi, int wi, int k, const float* w0, int n0, const float* w1, int n1,
+                         const float* bias0, const float* bias1, int transpose, int stride, int accumulate, float* c,
+                         int32_t* variant, void* stream) {
+  if (!a || !w0 || !c || ((w1 != nullptr) != (n1 > 0)) || (bias1 && !w1))
+    return op_fail(SVAE_EBADARG, "gconv_smalln: null pointer (w1 goes with n1 > 0, bias1 with w1)");
+  if (n <= 0 || hi <= 0 || wi <= 0 || k <= 0 || k > 256 || n0 < 1 || n1 < 0 || n0 + n1 > 4 || (stride != 1 && stride != 2))
+    return op_fail(SVAE_EBADARG, "gconv_smalln: sizes must be positive, k <= 256, n0 + n1 <= 4, stride 1|2");
+  if (!transpose && stride == 2 && (hi % 2 || wi % 2)) return op_fail(SVAE_EBADARG, "gconv_smalln: odd size at stride 2");
+  if (k % 4 == 0 && !al16(a)) return op_fail(SVAE_EBADARG, "gconv_smalln: k % 4 == 0 reads 16-byte rows of a");
+  const int ho = transpose ? hi * stride : hi / stride, wo = transpose ? wi * stride : wi / stride;
+  if ((long long)n * ho * wo > 0x7fffffffLL || (long long)n * hi * wi > 0x7fffffffLL)
+    return op_fail(SVAE_EBADARG, "gconv_smalln: too many pixels");
+  ConvGeom g{transpose ? GM_CONVT : GM_CONV, n, hi, wi, ho, wo, stride, 1, 4};
+  gconv_smalln(a, k, k, w0, n0, w1, n1, (long long)n0 * k, (long long)n1 * k, bias0, bias1, g, (long long)n * ho * wo, c,
+               n0 + n1, accumulate != 0, (hipStream_t)stream);
+  if (variant) {
+    variant[0] = g_gconv_last[0];
+    variant[1] = g_gconv_last[1];
+  }
+  return op_done();
+}
+
+int svae_op_gconv_variant(int k, int lda, int nout, int transpose, int stride, int ho, int wo, int32_t* variant) {
+  if (!variant) return op_fail(SVAE_EBADARG, "gconv_variant: null pointer");
+  if (k <= 0 || lda < k || nout <= 0 || nout > 4 || (stride != 1 && stride != 2) || ho <= 0 || wo <= 0)
+    return op_fail(SVAE_EBADARG, "gconv_variant: k, lda >= k, 1 <= nout <= 4, stride 1|2, ho, wo");
+  ConvGeom g{transpose ? GM_CONVT : GM_CONV, 1, 0, 0, ho, wo, stride, 1, 4};
+  int lp = 0;
+  variant[0] = gconv_smalln_path(k, lda, nout, g, &lp);
+  variant[1] = lp;
+  return 0;
+}
+
+int svae_op_output_fwd(const float* a, int b, int h, int w, int c, const float* xprev, const float* target, float lo,
+                       float hi, float minh, float maxh, const float* kl_img, float* xhat, float* rec_part,
+                       float* rec_img, float* stats, void* stream) {
+  if (!a || !target || !kl_img || !xhat || !rec_part || !rec_img || !stats)
+    return op_fail(SVAE_EBADARG, "output_fwd: null pointer");
+  if (b <= 0 || h <= 0 || w <= 0 || c < 1 || c > 4)
+    return op_fail(SVAE_EBADARG, "output_fwd: b, h, w must be positive and c in [1, 4]");
+  if (c == 3 && !al16(a)) return op_fail(SVAE_EBADARG, "output_fwd: c = 3 reads 16-byte rows of a");
+  hipStream_t s = (hipStream_t)stream;
+  const int nblk = output_blocks_per_img(h * w);
+  output_fwd(a, b, h * w, c, xprev, target, lo, hi, minh, maxh, xhat, rec_part, nblk, s);
+  loss_reduce(rec_part, nblk, kl_img, b, h * w * c, stats, rec_img, s);
+  return op_done();
+}
+
+int svae_op_output_bwd(const float* a, int b, int h, int w, int c, const float* xprev, const float* xhat,
+                       const float* target, float lo, float hi, float minh, float maxh, float rec_coef,
+                       const float* dxhat_in, float* da, float* dxprev, float* db_out, float* db_ratio, void* scratch,
+                       int64_t scratch_bytes, void* stream) {
+  if (!a || !xhat || !target || !da || !scratch || (xprev && !dxprev))
+    return op_fail(SVAE_EBADARG, "output_bwd: null pointer (dxprev is required with xprev)");
+  if (b <= 0 || h <= 0 || w <= 0 || c < 1 || c > 4)
+    return op_fail(SVAE_EBADARG, "output_bwd: b, h, w must be positive and c in [1, 4]");
+  // colsum_small sums at most 4 columns: c = 4 (wider than any model's image) has no bias gradients
+  if ((c <= 3) != (db_out != nullptr) || (c == 4 && db_ratio))
+    return op_fail(SVAE_EBADARG, "output_bwd: db_out is required for c <= 3 and both bias gradients are NULL for c = 4");
+  if (c == 3 && (!al16(a) || !al16(da))) return op_fail(SVAE_EBADARG, "output_bwd: c = 3 moves 16-byte rows of a and da");
+  if (scratch_bytes < 1024 * (int64_t)sizeof(float)) return op_fail(SVAE_EBADARG, "output_bwd: scratch below 1024 floats");
+  hipStream_t s = (hipStream_t)stream;
+  output_bwd(a, b, h * w, c, xprev, xhat, target, lo, hi, minh, maxh, rec_coef, dxhat_in, da, dxprev, s);
+  if (c <= 3) colsum_small(da, c + 1, (long long)b * h * w, c + 1, (float*)scratch, db_out, c, db_ratio, s);
+  return op_done();
+}
+
+}  // extern "C"

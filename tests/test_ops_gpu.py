@@ -29,6 +29,14 @@ CONV_CASES = [
 ]
 
 
+# input gradient only (svae_op_conv refuses cout % 4 != 0): the MNIST packed output conv-T [C | ratio] = 2 columns,
+# whose input gradient is a conv gather with K = 2
+DGRAD_ONLY_CASES = [
+    (2, 14, 32, 2, 2, 1),
+    (3, 7, 16, 2, 2, 1),
+]
+
+
 def _lib():
     return pkg_mod("_lib")
 
@@ -84,6 +92,22 @@ def test_conv_dgrad_wgrad(case):
     torch.cuda.synchronize()
     _close(dx, x.grad)
     _close(dw, w.grad, tol=5e-5)
+
+
+@pytest.mark.parametrize("case", DGRAD_ONLY_CASES)
+def test_conv_dgrad_packed_mnist_width(case):
+    n, h, cin, cout, s, tr = case
+    L = _lib()
+    x = _rand((n, h, h, cin), 3).double().requires_grad_(True)
+    w = (_rand((4, 4, cout, cin), 4) * 0.2).double()
+    y = _ref_conv(x, w, s, tr)
+    dy = _rand(tuple(y.shape), 5).double()
+    (y * dy).sum().backward()
+    dyd, wd = dy.float().cuda().contiguous(), w.float().cuda().contiguous()
+    dx = torch.zeros(n, h, h, cin, device="cuda")
+    L.check(L.lib().svae_op_conv_dgrad(L.ptr(dyd), n, h, cin, L.ptr(wd), cout, s, tr, L.ptr(dx), L.stream_ptr()))
+    torch.cuda.synchronize()
+    _close(dx, x.grad)
 
 
 @pytest.mark.parametrize("act", [0, 1, 2])
