@@ -784,6 +784,44 @@ int svae_op_pairwise_stats(const float* x, int64_t n, int64_t ldx, const float* 
                            const double* inv_two_sigma2, int n_bw, double* ksum, double* nn_d2, int64_t* nn_idx,
                            void* scratch, void* stream);
 
+/* Row-wise order statistics and ball counts of the same pairwise squared distances (no reference counterpart: the
+ * numbers behind quality.manifold, the k-NN precision / recall / density / coverage of NoisyTrainer.sample_quality).
+ * x, n, ldx, y, m, ldy, n_groups, d and self_group are svae_op_pairwise_stats' own, and so is d2(i, j), bit for bit
+ * (csrc/pairwise_tile.h: the two ops share the norms and the distance tile): max(0, (a_i + b_j) - 2 g_ij) in fp64,
+ * the norms summed in fp64 in an order fixed by d, g_ij on v_mfma_f32_32x32x2_f32 in ascending k, a non-finite value
+ * NaN.  radius2 is a HOST array of n_groups device pointers, entry g [m[g]][n_radii] fp64: the squared radii of
+ * column j of group g; a NULL entry: that group has no radii.  Per row i and group g, over the group's admitted
+ * columns (all but (i, i) of the self group), the outputs (device; nothing else is written) are
+ *   knn_d2   [n][n_groups][k]       (fp64)  = the k smallest d2(i, j) in ascending order (values, not columns: ties
+ *                                             cannot make it ambiguous), +inf where fewer than k columns are admitted,
+ *   inside   [n][n_groups][n_radii] (int64) = the number of admitted columns j with d2(i, j) <= radius2[g][j][r]; a
+ *                                             NaN radius admits nothing, a +inf radius every finite d2, a group
+ *                                             without radii gives 0,
+ *   nonfinite[n][n_groups]          (int64) = the number of admitted pairs whose d2 is NaN; may be NULL.
+ * A pair whose d2 is NaN enters neither knn_d2 nor inside: it is counted, not propagated.  That differs from
+ * svae_op_pairwise_stats, where a NaN spoils the sums and the minimum of the rows that read it: a sum has no
+ * answer without the term, an order statistic and a count over the remaining pairs have one, and nonfinite says
+ * how many pairs they leave out.  knn_d2 (with k == 0) or inside (with n_radii == 0) may be NULL to skip that part;
+ * a part computed alone has the bytes it has beside the other.  knn_d2[.][.][0] has the bytes of
+ * svae_op_pairwise_stats' nn_d2 wherever no admitted pair is NaN.
+ * Row i of every output depends on x[i], the groups and the radii only: not on n, on the other rows, on the row tile
+ * or the grid, or on an address; two calls give the same bytes.  No atomics, no allocation, no synchronisation; the
+ * launches go on `stream`; the caller provides svae_op_knn_scratch_bytes(n, m, n_groups, k, n_radii) bytes of
+ * 8-byte aligned device scratch (norms and per-column-tile partials).
+ * SVAE_EBADARG (checked on the host before any launch): a null required pointer, n, d, n_groups or an m[g] <= 0, a
+ * leading dimension < d, k < 0 or n_radii < 0, k == 0 with knn_d2 or k > 0 without, n_radii == 0 with inside or
+ * n_radii > 0 without inside or without radius2, nothing to compute, self_group >= n_groups or set with
+ * n != m[self_group] or x != y[self_group], null scratch.  SVAE_EBADCONFIG: n_groups > SVAE_PAIRWISE_MAX_GROUPS,
+ * k > SVAE_KNN_MAX_K, n_radii > SVAE_KNN_MAX_RADII, d > 2^31 - 1, more than 65535 row tiles or 2^31 - 1 column
+ * tiles.  svae_op_knn_scratch_bytes returns -1 for arguments the op would reject. */
+#define SVAE_KNN_MAX_K 8
+#define SVAE_KNN_MAX_RADII 4
+int64_t svae_op_knn_scratch_bytes(int64_t n, const int64_t* m, int n_groups, int k, int n_radii);
+int svae_op_pairwise_knn(const float* x, int64_t n, int64_t ldx, const float* const* y, const int64_t* m,
+                         const int64_t* ldy, int n_groups, int64_t d, int self_group, int k, double* knn_d2,
+                         const double* const* radius2, int n_radii, int64_t* inside, int64_t* nonfinite,
+                         void* scratch, void* stream);
+
 /* Binned power spectra of a stack of images and of their differences to reference images, one launch on `stream`
  * (no allocation, no synchronisation; no reference counterpart: the numbers behind NoisyTrainer.spectrum).
  * x [n, h, w, c] and y [ny, h, w, c] or NULL are fp32 NHWC on the device at any alignment; image i of x is paired

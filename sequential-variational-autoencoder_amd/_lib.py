@@ -77,6 +77,8 @@ SSIM_WINDOW, SSIM_SIGMA, SSIM_K1, SSIM_K2, METRICS_TILE = 11, 1.5, 0.01, 0.03, 1
 LATENTS_TILE, LATENTS_MAX_DIM, LATENTS_MAX_SEGMENTS = 16, 256, 1024
 # svae_op_pairwise_stats (include/svae_hip.h): SVAE_PAIRWISE_TILE_ROWS, _TILE_COLS, _TILE_K, _MAX_GROUPS, _MAX_BW
 PAIRWISE_TILE_ROWS, PAIRWISE_TILE_COLS, PAIRWISE_TILE_K, PAIRWISE_MAX_GROUPS, PAIRWISE_MAX_BW = 128, 128, 32, 4, 8
+# svae_op_pairwise_knn (include/svae_hip.h): SVAE_KNN_MAX_K, _MAX_RADII
+KNN_MAX_K, KNN_MAX_RADII = 8, 4
 # svae_op_power_spectrum (include/svae_hip.h): SVAE_SPECTRUM_MAX_DIM, _MAX_BINS
 SPECTRUM_MAX_DIM, SPECTRUM_MAX_BINS = 96, 64
 
@@ -179,6 +181,9 @@ def _load(path):
         "svae_op_pairwise_scratch_bytes": ([i64, ctypes.POINTER(i64), i32, i32], i64),
         "svae_op_pairwise_stats": ([vp, i64, i64, ctypes.POINTER(vp), ctypes.POINTER(i64), ctypes.POINTER(i64), i32, i64,
                                     i32, ctypes.POINTER(ctypes.c_double), i32, vp, vp, vp, vp, vp], i32),
+        "svae_op_knn_scratch_bytes": ([i64, ctypes.POINTER(i64), i32, i32, i32], i64),
+        "svae_op_pairwise_knn": ([vp, i64, i64, ctypes.POINTER(vp), ctypes.POINTER(i64), ctypes.POINTER(i64), i32, i64,
+                                  i32, i32, vp, ctypes.POINTER(vp), i32, vp, vp, vp, vp], i32),
         "svae_op_power_spectrum": ([vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp], i32),
         "svae_op_heads_splits": ([i32], i32),
         "svae_op_heads_fwd": ([vp, i32, i32, vp, vp, i64, i32, vp, i32, i32, i32, i32, ctypes.POINTER(i32), vp], i32),
@@ -296,7 +301,8 @@ EXPORTED = ["svae_param_count", "svae_param_layout", "svae_create", "svae_destro
             "svae_op_gconv_variant", "svae_op_gconv_last_kernel", "svae_op_gconv_smalln", "svae_op_output_convt",
             "svae_op_output_fwd", "svae_op_output_bwd",
             "svae_op_sd_layer", "svae_op_sd_layer_bwd", "svae_op_sd_head_fwd", "svae_op_sd_head_bwd",
-            "svae_op_chain_noise", "svae_op_imp_seed", "svae_op_sqdiff_img"]
+            "svae_op_chain_noise", "svae_op_imp_seed", "svae_op_sqdiff_img",
+            "svae_op_knn_scratch_bytes", "svae_op_pairwise_knn"]
 # include/svae_pcnn.h (the PixelCNN++ head)
 PCNN_EXPORTED = ["svae_pcnn_wnorm", "svae_pcnn_wnorm_bwd", "svae_pcnn_conv", "svae_pcnn_conv_wgrad", "svae_pcnn_colsum",
                  "svae_pcnn_colsum_absmax", "svae_pcnn_im2col_h16", "svae_pcnn_conv_planes_amax",

@@ -18,8 +18,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 OUT = os.path.join(HERE, "libsvae_hip.so")
-SOURCES = ["gemm.hip", "gemm_bf16.hip", "wgrad_halo2.hip", "wgrad_smallc.hip", "smallc.hip", "bn.hip", "misc.hip", "chain.hip", "flat.hip", "halo_kw.hip", "halo_x3.hip", "dense_kw.hip", "pcnn.hip", "batch.hip", "degrade.hip", "crops.hip", "jpeg.hip", "tiles.hip", "stats.hip", "metrics.hip", "latents.hip", "pairwise.hip", "spectrum.hip", "ema.hip", "engine.cpp"]
-HEADERS = ["common.h", "corrupt.h", "kernels.h", "knobs.h", "opentry.h", "opload.h", "philox.h", "pixel.h"]
+SOURCES = ["gemm.hip", "gemm_bf16.hip", "wgrad_halo2.hip", "wgrad_smallc.hip", "smallc.hip", "bn.hip", "misc.hip", "chain.hip", "flat.hip", "halo_kw.hip", "halo_x3.hip", "dense_kw.hip", "pcnn.hip", "batch.hip", "degrade.hip", "crops.hip", "jpeg.hip", "tiles.hip", "stats.hip", "metrics.hip", "latents.hip", "pairwise.hip", "knn.hip", "spectrum.hip", "ema.hip", "engine.cpp"]
+HEADERS = ["common.h", "corrupt.h", "kernels.h", "knobs.h", "opentry.h", "opload.h", "pairwise_tile.h", "philox.h", "pixel.h"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-mcode-object-version=5",
          "-I" + INCLUDE, "-I" + CSRC, "-Wno-unused-result"]

@@ -5,17 +5,13 @@
 //   d2(i, j) = max(0, (a_i + b_j) - 2 g_ij)      a, b: squared norms in fp64, g: the fp32 inner product
 //
 // Three kernels, all on the caller's stream, no atomics:
-//  1. pw_norms: one wave per row.  Lane l adds (double)v * v over k = l, l + 64, ... in ascending k, then a
-//     butterfly over the 64 lanes (xor 32, 16, ... 1): the order depends on d alone.
+//  1. pw_norms (pairwise_tile.h): the squared norms, one wave per row, in an order that depends on d alone.
 //  2. pw_tile<RT>: one block of four waves per (row tile, column tile) of RT x PW_C = 128 x 128, column tiles
 //     counted through the groups one after the other (a tile never spans two groups).  Where that grid has fewer
 //     blocks than the device has CUs (PW_FILL), the row tile is RT = 32 instead, a wave owning 32 x 32: four
-//     times the blocks.  A row's arithmetic does not know the row tile, so this changes no byte of the output.  The K loop stages
-//     PW_K = 32 dimensions of both operands in LDS, k-major ([k][row], stride 130: the 32 k of one row that a
-//     half-wave loads land in 32 banks two apart, and the 32 rows a half-wave reads in 32 consecutive banks),
-//     with the next slab's global loads in flight in registers during the MFMAs; a wave owns 64 x 64 of the
-//     tile as 2 x 2 accumulators of v_mfma_f32_32x32x2_f32, so g_ij is an fmaf chain in ascending k from 0
-//     (rows, columns and dimensions past the end are staged as zeros, which add nothing).  Two blocks fit a CU
+//     times the blocks.  A row's arithmetic does not know the row tile, so this changes no byte of the output.
+//     The staging, the MFMA K loop and the accumulator tile are pw_gram_tile<RT> (pairwise_tile.h, shared with
+//     knn.hip): g_ij is an fmaf chain in ascending k from 0 on v_mfma_f32_32x32x2_f32.  Two blocks fit a CU
 //     (77 KB of LDS, 179 VGPRs): one block's loads and epilogue hide behind the other's MFMAs.
 //     Epilogue: the accumulators go to LDS as a [RT][129] fp32 tile (over the staging area); thread t < 2 RT owns
 //     row t % RT and the column half t / RT and walks its 64 columns in ascending j: d2 in fp64, the clamp,
@@ -33,45 +29,18 @@
 
 #include "common.h"
 #include "opentry.h"
+#include "pairwise_tile.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int PW_R = SVAE_PAIRWISE_TILE_ROWS;
-constexpr int PW_C = SVAE_PAIRWISE_TILE_COLS;
-constexpr int PW_K = SVAE_PAIRWISE_TILE_K;
-constexpr int PW_G = SVAE_PAIRWISE_MAX_GROUPS;
 constexpr int PW_B = SVAE_PAIRWISE_MAX_BW;
-constexpr int PW_THREADS = 256;
-constexpr double PW_DBL_MAX = 1.7976931348623157e308;
-constexpr int PW_LD = 130;                       // staging stride in floats
-constexpr int PW_GLD = PW_C + 1;                 // accumulator tile stride in floats
-constexpr int PW_PER = PW_C * PW_K / PW_THREADS; // staged floats per thread of the column operand
-constexpr int PW_FILL = 256;                     // blocks below which the small row tile is taken
-static_assert(PW_R == 128 && PW_C == 128 && PW_K == 32, "the lane maps below are written for 128 x 128 x 32");
 
-struct PwArgs {
-  const float* y[PW_G];
-  long long m[PW_G], ldy[PW_G];
-  long long boff[PW_G];  // the group's first norm in bn
-  int ct0[PW_G + 1];     // the group's first column tile; ct0[n_groups] = all of them
+struct PwArgs : PwGroups {
   double inv[PW_B];
-  int n_groups, n_bw, self_group;
+  int n_bw;
 };
-
-__global__ __launch_bounds__(64) void pw_norms(const float* __restrict__ x, long long ld, int d,
-                                               double* __restrict__ out) {
-  const float* row = x + (long long)blockIdx.x * ld;
-  double s = 0.0;
-  for (int k = threadIdx.x; k < d; k += 64) {
-    const double v = (double)row[k];
-    s = s + v * v;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s = s + __shfl_xor(s, o, 64);
-  if (threadIdx.x == 0) out[blockIdx.x] = s;
-}
 
 // the running minimum: the first NaN wins and stays, otherwise the first smallest value
 __device__ __forceinline__ void pw_min(double& best, long long& idx, double v, long long j) {
@@ -88,89 +57,18 @@ __global__ __launch_bounds__(PW_THREADS, 2) void pw_tile(const float* __restrict
                                                          const double* __restrict__ bn, PwArgs A,
                                                          double* __restrict__ pk, double* __restrict__ pd,
                                                          long long* __restrict__ pi) {
-  static_assert(RT == 128 || RT == 32, "row tiles of 128 (2 x 2 waves of 64 x 64) or 32 (1 x 4 waves of 32 x 32)");
-  constexpr int WCOLS = RT == 128 ? 2 : 4;             // waves side by side
-  constexpr int MI = RT == 128 ? 2 : 1, NJ = PW_C / (32 * WCOLS);  // 32 x 32 accumulators per wave: MI x NJ
-  constexpr int PER_A = RT * PW_K / PW_THREADS;        // staged floats per thread of the row operand
-  constexpr int LDS_FLOATS = RT * PW_GLD > 2 * PW_K * PW_LD ? RT * PW_GLD : 2 * PW_K * PW_LD;
-  __shared__ float lds[LDS_FLOATS];                    // staging [2][PW_K][PW_LD], then the [RT][PW_GLD] tile
+  __shared__ float lds[pw_lds_floats<RT>()];          // pw_gram_tile's staging, then the [RT][PW_GLD] tile
   __shared__ double bs[PW_C];                          // the tile's column norms
   __shared__ double hk[RT][PW_B];                      // column half 1's sums, minimum and index
   __shared__ double hd[RT];
   __shared__ long long hi[RT];
-  float* As = lds;
-  float* Bs = lds + PW_K * PW_LD;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int ct = blockIdx.x;
-  int g = 0;
-  while (g + 1 < A.n_groups && ct >= A.ct0[g + 1]) ++g;
+  const int g = pw_group_of(A, ct);
   const long long row0 = (long long)blockIdx.y * RT;
   const long long col0 = (long long)(ct - A.ct0[g]) * PW_C;
-  const float* __restrict__ y = A.y[g];
-  const long long m = A.m[g], ldy = A.ldy[g];
-
-  // staging map: thread t loads dimension t % 32 of rows (columns) t / 32 + 8 e, e < RT / 8 (16)
-  const int sk = tid & (PW_K - 1), sr = tid / PW_K;
-  float ra[PER_A], rb[PW_PER];
-  auto fetch = [&](int k0) {
-    const bool kin = k0 + sk < d;
-#pragma unroll
-    for (int e = 0; e < PER_A; ++e) {
-      const long long r = row0 + sr + 8 * e;
-      ra[e] = kin && r < n ? x[r * ldx + k0 + sk] : 0.f;
-    }
-#pragma unroll
-    for (int e = 0; e < PW_PER; ++e) {
-      const long long c = col0 + sr + 8 * e;
-      rb[e] = kin && c < m ? y[c * ldy + k0 + sk] : 0.f;
-    }
-  };
-  // MFMA map (32x32x2): lane l gives A[row l % 32][k l / 32] and B[k l / 32][col l % 32]
-  const int wr = (wave / WCOLS) * 32 * MI, wc = (wave % WCOLS) * 32 * NJ, li = lane & 31, lk = lane >> 5;
-  f32x16 acc[MI][NJ];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  fetch(0);
-  for (int k0 = 0; k0 < d; k0 += PW_K) {
-    __syncthreads();  // the previous slab's readers are done
-#pragma unroll
-    for (int e = 0; e < PER_A; ++e) As[sk * PW_LD + sr + 8 * e] = ra[e];
-#pragma unroll
-    for (int e = 0; e < PW_PER; ++e) Bs[sk * PW_LD + sr + 8 * e] = rb[e];
-    __syncthreads();
-    if (k0 + PW_K < d) fetch(k0 + PW_K);
-#pragma unroll
-    for (int ks = 0; ks < PW_K; ks += 2) {
-      const float* ap = As + (ks + lk) * PW_LD + wr + li;
-      const float* bp = Bs + (ks + lk) * PW_LD + wc + li;
-      float av[MI], bv[NJ];
-#pragma unroll
-      for (int i = 0; i < MI; ++i) av[i] = ap[32 * i];
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) bv[j] = bp[32 * j];
-#pragma unroll
-      for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[j], acc[i][j], 0, 0, 0);
-    }
-  }
-  __syncthreads();  // the last slab's readers are done: the staging area becomes the tile
-  // D[row (r % 4) + 8 (r / 4) + 4 (l / 32)][col l % 32]
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r)
-        lds[(wr + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lk) * PW_GLD + wc + 32 * j + li] = acc[i][j][r];
-  if (tid < PW_C) bs[tid] = col0 + tid < m ? bn[A.boff[g] + col0 + tid] : 0.0;
-  __syncthreads();
+  const long long m = A.m[g];
+  pw_gram_tile<RT>(x, n, ldx, d, A.y[g], m, A.ldy[g], bn + A.boff[g], row0, col0, lds, bs);
 
   const int er = tid & (RT - 1), half = tid / RT;  // half >= 2 (RT = 32): nothing to walk, nothing to store
   const long long row = row0 + er;
@@ -184,9 +82,7 @@ __global__ __launch_bounds__(PW_THREADS, 2) void pw_tile(const float* __restrict
   const int c1 = half < 2 ? (int)min((long long)(half * 64 + 64), m - col0) : 0;
   for (int c = half * 64; c < c1; ++c) {
     if (col0 + c == skip) continue;
-    double d2 = (a + bs[c]) - 2.0 * (double)lds[er * PW_GLD + c];
-    // the clamp; +-inf (an inf element, or an fp32 inner product that overflowed) is NaN like a NaN itself
-    d2 = fabs(d2) <= PW_DBL_MAX ? (d2 < 0.0 ? 0.0 : d2) : (double)NAN;
+    const double d2 = pw_d2(a, bs, lds, er, c);
     if (pk) {
 #pragma unroll
       for (int l = 0; l < PW_B; ++l)
@@ -243,12 +139,6 @@ __global__ __launch_bounds__(256) void pw_reduce(long long n, PwArgs A, const do
   }
 }
 
-long long pw_tiles(const int64_t* m, int n_groups) {
-  long long t = 0;
-  for (int g = 0; g < n_groups; ++g) t += (m[g] + PW_C - 1) / PW_C;
-  return t;
-}
-
 // scratch: a [n] and b [sum m] norms, then per (column tile, row) the n_bw sums, the minimum and its index
 long long pairwise_scratch_bytes(long long n, const int64_t* m, int n_groups, int n_bw) {
   long long cols = 0;
@@ -261,29 +151,15 @@ void pairwise_stats(const float* x, long long n, long long ldx, const float* con
                     const int64_t* ldy, int n_groups, int d, int self_group, const double* inv_two_sigma2,
                     int n_bw, double* ksum, double* nn_d2, long long* nn_idx, void* scratch, hipStream_t s) {
   PwArgs A = {};
-  A.n_groups = n_groups;
+  const long long cols = pw_groups(A, y, m, ldy, n_groups, self_group);
   A.n_bw = n_bw;
-  A.self_group = self_group;
-  long long cols = 0;
-  for (int g = 0; g < n_groups; ++g) {
-    A.y[g] = y[g];
-    A.m[g] = m[g];
-    A.ldy[g] = ldy[g];
-    A.boff[g] = cols;
-    A.ct0[g + 1] = A.ct0[g] + (int)((m[g] + PW_C - 1) / PW_C);
-    cols += m[g];
-  }
   for (int l = 0; l < n_bw; ++l) A.inv[l] = inv_two_sigma2[l];
   const long long tiles = A.ct0[n_groups];
-  double* an = (double*)scratch;
-  double* bn = an + n;
+  double* bn = (double*)scratch + n;
   double* pk = bn + cols;
   double* pd = pk + tiles * n * n_bw;
   long long* pi = (long long*)(pd + tiles * n);
-  for (int g = 0; g < n_groups; ++g)
-    hipLaunchKernelGGL(pw_norms, dim3((unsigned)m[g]), dim3(64), 0, s, y[g], ldy[g], d, bn + A.boff[g]);
-  if (self_group >= 0) an = bn + A.boff[self_group];  // the same rows: the same bytes
-  else hipLaunchKernelGGL(pw_norms, dim3((unsigned)n), dim3(64), 0, s, x, ldx, d, an);
+  const double* an = pw_launch_norms(x, n, ldx, d, A, (double*)scratch, bn, s);
   const long long rt128 = (n + PW_R - 1) / PW_R;
   if (rt128 * tiles >= PW_FILL)
     hipLaunchKernelGGL(pw_tile<PW_R>, dim3((unsigned)tiles, (unsigned)rt128), dim3(PW_THREADS), 0, s, x, n, ldx, d, an,
@@ -296,14 +172,7 @@ void pairwise_stats(const float* x, long long n, long long ldx, const float* con
 }
 
 bool pairwise_shape_ok(int64_t n, const int64_t* m, int n_groups, int n_bw) {
-  if (!m || n <= 0 || n_groups <= 0 || n_groups > SVAE_PAIRWISE_MAX_GROUPS || n_bw < 0 || n_bw > SVAE_PAIRWISE_MAX_BW)
-    return false;
-  int64_t tiles = 0;
-  for (int g = 0; g < n_groups; ++g) {
-    if (m[g] <= 0) return false;
-    tiles += (m[g] + SVAE_PAIRWISE_TILE_COLS - 1) / SVAE_PAIRWISE_TILE_COLS;
-  }
-  return tiles <= 2147483647LL && (n + SVAE_PAIRWISE_TILE_ROWS - 1) / SVAE_PAIRWISE_TILE_ROWS <= 65535;
+  return n_bw >= 0 && n_bw <= SVAE_PAIRWISE_MAX_BW && pw_shape_ok(n, m, n_groups);
 }
 
 }  // namespace

@@ -14,6 +14,24 @@ With k_s(a, b) = exp(-|a - b|^2 / (2 s^2)), x [n, d] and y [m, d]:
 
 at the bandwidths s^2 = sigma0^2 * SCALES, sigma0^2 the mean squared distance between distinct points of y
 (bandwidths(): closed form from the first two moments, no [m, m] pass).
+
+Those numbers say that two sets differ, not how.  The k-nearest-neighbour manifold metrics split the difference into
+fidelity and diversity: improved precision and recall (Kynkaanniemi et al. 2019) and their outlier-robust versions,
+density and coverage (Naeem et al. 2020), on svae_op_pairwise_knn (csrc/knn.hip: the k smallest squared distances
+per row and the number of per-column balls a row falls into, on the same distance tile, again with no [n, m]
+intermediate and no torch formulation behind it).  With r_k(p)^2 the squared distance of p to its k-th nearest
+OTHER point of its own set, inside(p; S, r) = #{s in S : |p - s|^2 <= r(s)^2}, x [n, d] the samples and y [m, d]
+the real points (manifold()):
+
+    precision_k = mean_i [ inside(x_i; y, r_k(y)) > 0 ]     the share of samples inside the real manifold (fidelity)
+    density_k   = mean_i   inside(x_i; y, r_k(y)) / k       how many real balls hold a sample; 1 in expectation for
+                                                            one distribution, unbounded above
+    recall_k    = mean_j [ inside(y_j; x, r_k(x)) > 0 ]     the share of real points inside the sample manifold
+    coverage_k  = mean_j [ min_i |y_j - x_i|^2 <= r_k(y_j)^2 ]   the share of real balls that hold a sample (diversity)
+
+All comparisons are on squared distances.  These are manifolds in PIXEL space, as crude as pixel-space MMD: the
+papers measure in the feature space of a pretrained network, which this project does without.  Read them against
+the calibration line the report gives (held-out real images against training images), not against 1.
 """
 import ctypes
 
@@ -23,15 +41,16 @@ from . import _lib
 
 TILE_ROWS, TILE_COLS, TILE_K = _lib.PAIRWISE_TILE_ROWS, _lib.PAIRWISE_TILE_COLS, _lib.PAIRWISE_TILE_K
 MAX_GROUPS, MAX_BW = _lib.PAIRWISE_MAX_GROUPS, _lib.PAIRWISE_MAX_BW
+KNN_MAX_K, KNN_MAX_RADII = _lib.KNN_MAX_K, _lib.KNN_MAX_RADII
 SCALES = (0.25, 0.5, 1.0, 2.0, 4.0)
 
 _scratch = {}  # device -> kept uint8 scratch tensor (grown, never shrunk)
 
 
-def _rows(t, what):
+def _rows(t, what, op="pairwise_stats"):
     if t.dim() != 2 or t.dtype != torch.float32 or not t.is_cuda or t.shape[0] < 1 or t.shape[1] < 1 \
             or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
-        raise ValueError("pairwise_stats takes %s as a float32 [rows, d] GPU tensor with contiguous rows" % what)
+        raise ValueError("%s takes %s as a float32 [rows, d] GPU tensor with contiguous rows" % (op, what))
     return int(t.stride(0)) if t.shape[0] > 1 else max(int(t.stride(0)), int(t.shape[1]))
 
 
@@ -89,6 +108,58 @@ def pairwise_stats(x, groups, bandwidths, self_group=None, out=None, ksum=True, 
         None if scratch is None else ctypes.c_void_p(scratch.data_ptr()),
         _lib.stream_ptr(torch.cuda.current_stream(dev))))
     return ks, nd, ni
+
+
+def knn_stats(x, groups, k, radii=None, self_group=None, out=None):
+    """(knn_d2 [n, G, k] fp64, inside [n, G, n_radii] int64, nonfinite [n, G] int64) device tensors of
+    svae_op_pairwise_knn for the rows x [n, d] against the column groups ``groups`` (a list of [m_g, d] tensors, as
+    pairwise_stats takes them): the k smallest squared distances in ascending order (+inf past the admitted
+    columns), the number of columns j whose squared radius radii[g][j, r] is at least the distance, and the number of
+    NaN distances, which enter neither.  ``radii``: a list with one [m_g, n_radii] contiguous fp64 tensor or None
+    (no radii for that group: its counts are 0) per group, or None for no counts at all; ``k`` = 0 skips the
+    distances.  A skipped part is returned as None.  ``self_group`` = g: x is groups[g] itself and the pairs (i, i)
+    are left out.  ``out``: a dict with any of "knn_d2", "inside", "nonfinite" to write into.  The launches go to
+    x's device's current stream, nothing synchronises; the scratch is pairwise_stats' own kept one."""
+    ldx = _rows(x, "x", "knn_stats")
+    groups = list(groups)
+    G, n, d, k = len(groups), int(x.shape[0]), int(x.shape[1]), int(k)
+    ldy = [_rows(y, "group %d" % g, "knn_stats") for g, y in enumerate(groups)]
+    for y in groups:
+        if y.device != x.device or y.shape[1] != d:
+            raise ValueError("knn_stats takes groups of x's width on x's device")
+    radii = [None] * G if radii is None else list(radii)
+    if len(radii) != G:
+        raise ValueError("knn_stats takes one radii tensor (or None) per group")
+    nr = 0
+    for g, r in enumerate(radii):
+        if r is None:
+            continue
+        if r.dim() != 2 or r.dtype != torch.float64 or r.device != x.device or not r.is_contiguous() \
+                or r.shape[0] != groups[g].shape[0] or r.shape[1] < 1 or (nr and r.shape[1] != nr):
+            raise ValueError("knn_stats takes radii[%d] as a contiguous float64 [m_g, n_radii] tensor on x's device, "
+                             "n_radii the same for every group" % g)
+        nr = int(r.shape[1])
+    sg = -1 if self_group is None else int(self_group)
+    dev = x.device
+    m = (ctypes.c_int64 * max(1, G))(*[int(y.shape[0]) for y in groups])
+    L = _lib.lib()
+    need = int(L.svae_op_knn_scratch_bytes(n, m, G, k, nr))
+    scratch = _scratch.get(dev)
+    if need > 0 and (scratch is None or scratch.numel() < need):
+        _scratch[dev] = scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    kd = _out(out, "knn_d2", (n, G, k), torch.float64, dev) if k > 0 else None
+    ins = _out(out, "inside", (n, G, nr), torch.int64, dev) if nr > 0 else None
+    nf = _out(out, "nonfinite", (n, G), torch.int64, dev)
+    yp = (ctypes.c_void_p * max(1, G))(*[y.data_ptr() for y in groups])
+    ld = (ctypes.c_int64 * max(1, G))(*ldy)
+    rp = (ctypes.c_void_p * max(1, G))(*[None if r is None else r.data_ptr() for r in radii])
+    _lib.check(L.svae_op_pairwise_knn(
+        ctypes.c_void_p(x.data_ptr()), n, ldx, yp, m, ld, G, d, sg, k,
+        None if kd is None else ctypes.c_void_p(kd.data_ptr()), rp if nr > 0 else None, nr,
+        None if ins is None else ctypes.c_void_p(ins.data_ptr()), ctypes.c_void_p(nf.data_ptr()),
+        None if scratch is None else ctypes.c_void_p(scratch.data_ptr()),
+        _lib.stream_ptr(torch.cuda.current_stream(dev))))
+    return kd, ins, nf
 
 
 def bandwidths(real):
@@ -166,3 +237,63 @@ def two_sample(x, y, yy=None, bw=None):
     rep = unpack(row, len(bw))
     rep["sigma0"] = float(bw[len(bw) // 2]) ** 0.5
     return rep
+
+
+def _ks(ks, n, m):
+    ks = [int(k) for k in ks]
+    if not ks or len(ks) > KNN_MAX_RADII or any(k < 1 or k > KNN_MAX_K for k in ks):
+        raise ValueError("manifold takes 1 to %d values of k in 1 .. %d, got %r" % (KNN_MAX_RADII, KNN_MAX_K, ks))
+    if min(n, m) < max(ks) + 1:
+        raise ValueError("manifold at k = %d needs %d points per set, got %d and %d" % (max(ks), max(ks) + 1, n, m))
+    return ks
+
+
+def self_radii(y, ks):
+    """What manifold keeps of a set against itself: (r2 [m, len(ks)] fp64, the squared distance of every point to
+    its k-th nearest other point for k in ``ks``, and the number of NaN distances met, a 0-dim int64 tensor).
+    ``y`` must be the centred copy manifold would make (center())."""
+    ks = _ks(ks, int(y.shape[0]), int(y.shape[0]))
+    kd, _, nf = knn_stats(y, [y], max(ks), self_group=0)
+    return kd[:, 0, [k - 1 for k in ks]].contiguous(), nf.sum()
+
+
+def manifold_device(xc, yc, ks=(3, 5), yy=None):
+    """manifold's numbers for centred sets as one flat fp64 device tensor: [precision (len(ks)), recall, density,
+    coverage, non-finite count].  ``yy`` = self_radii(yc, ks) of an earlier call with the same y and ks reuses the
+    y-against-y pass."""
+    n, m = int(xc.shape[0]), int(yc.shape[0])
+    ks = _ks(ks, n, m)
+    col = [k - 1 for k in ks]
+    ry, bad = self_radii(yc, ks) if yy is None else yy
+    kx, ix, nx = knn_stats(xc, [xc, yc], max(ks), radii=[None, ry], self_group=0)
+    rx = kx[:, 0, col].contiguous()
+    ky, iy, ny = knn_stats(yc, [xc], 1, radii=[rx])
+    kk = torch.tensor(ks, dtype=torch.float64, device=xc.device)
+    hit = ix[:, 1].double()
+    precision = (ix[:, 1] > 0).double().mean(0)
+    density = hit.sum(0) / (kk * n)
+    recall = (iy[:, 0] > 0).double().mean(0)
+    coverage = (ky[:, 0, :1] <= ry).double().mean(0)
+    bad = bad + nx.sum() + ny.sum()
+    return torch.cat([precision, recall, density, coverage, bad.double().reshape(1)])
+
+
+def unpack_manifold(row, ks):
+    """manifold's dict from manifold_device's table as a host list."""
+    nk = len(ks)
+    return {"k": [int(k) for k in ks], "precision": [float(v) for v in row[:nk]],
+            "recall": [float(v) for v in row[nk:2 * nk]], "density": [float(v) for v in row[2 * nk:3 * nk]],
+            "coverage": [float(v) for v in row[3 * nk:4 * nk]], "nonfinite": int(row[4 * nk])}
+
+
+def manifold(x, y, ks=(3, 5), yy=None):
+    """{"k": [..], "precision": [..], "recall": [..], "density": [..], "coverage": [..], "nonfinite"} for the samples
+    x [n, d] against the real points y [m, d] (float32, one GPU), one value per k in ``ks`` (at most KNN_MAX_RADII
+    values in 1 .. KNN_MAX_K; every set needs max(ks) + 1 points), by the module docstring's definitions.  y's mean
+    row is subtracted from both in copies; three knn_stats calls (y against itself; x against {x itself, y with
+    y's radii}; y against x with x's radii), then a few fp64 torch reductions and one device -> host copy.
+    "nonfinite" counts the NaN distances the three calls met: they enter no number.  ``yy`` = self_radii(centred
+    y, ks) of an earlier call reuses the y-against-y pass."""
+    xc, yc = center(x, y)
+    ks = _ks(ks, int(x.shape[0]), int(y.shape[0]))
+    return unpack_manifold(manifold_device(xc, yc, ks, yy=yy).cpu().tolist(), ks)

@@ -49,7 +49,7 @@ class NoisyTrainer:
     def __init__(self, network, dataset, denoise_train=False, vis_frequency=1000, plot_reconstruction=False,
                  base_dir=None, logger=None, seed=0, summary_freq=0, eval_frequency=0, info_frequency=0,
                  quality_frequency=0, degradation=None, spectrum_frequency=0, ema_decay=None, ema_warmup=True,
-                 ema_every=1):
+                 ema_every=1, quality_k=None):
         if list(dataset.data_dims) != list(network.data_dims):
             raise ValueError("dataset images %s, network %s" % (dataset.data_dims, network.data_dims))
         if tuple(dataset.range) != tuple(float(v) for v in network.cfg.range):
@@ -87,6 +87,9 @@ class NoisyTrainer:
         # every quality_frequency-th step appends sample_quality() to <base_dir>/sample_quality.jsonl; 0: none, and
         # the loop is exactly what it is without this option
         self.quality_frequency = int(quality_frequency)
+        # a tuple of k: the periodic sample_quality() carries the k-nearest-neighbour manifold metrics (its
+        # manifold_k); None: the report is exactly what it is without this option
+        self.quality_k = None if quality_k is None else tuple(int(k) for k in quality_k)
         # every spectrum_frequency-th step appends spectrum() to <base_dir>/spectrum.jsonl; 0: none, and the loop is
         # exactly what it is without this option
         self.spectrum_frequency = int(spectrum_frequency)
@@ -210,7 +213,7 @@ class NoisyTrainer:
         if self.info_frequency > 0 and self.iteration % self.info_frequency == 0:
             self.write_latent_information()
         if self.quality_frequency > 0 and self.iteration % self.quality_frequency == 0:
-            self.write_sample_quality()
+            self.write_sample_quality(**({} if self.quality_k is None else {"manifold_k": self.quality_k}))
         if self.spectrum_frequency > 0 and self.iteration % self.spectrum_frequency == 0:
             self.write_spectrum()
         return loss
@@ -499,7 +502,8 @@ class NoisyTrainer:
                 noise = torch.randn([T, B, H, W, C], generator=gen, dtype=torch.float32, device=self.device)
             yield w, net.generate(z, noise=noise)
 
-    def sample_quality(self, split="test", num_batches=None, seed=None, train_images=None, weights="train"):
+    def sample_quality(self, split="test", num_batches=None, seed=None, train_images=None, weights="train",
+                       manifold_k=None):
         """Per chain step, how close generated samples x_hat_t are to held-out images and whether they copy
         training images: the kernel MMD^2 two-sample estimate, the leave-one-out 1-nearest-neighbour two-sample
         accuracy and nearest-neighbour distances (quality.two_sample), all on svae_op_pairwise_stats.
@@ -532,7 +536,15 @@ class NoisyTrainer:
 
         with every distance a per-element RMS, sqrt(d2 / D), and sigma0 in the units of d (not per element).
         generate invalidates the network's last training forward: summaries() must be read before (step() does).
-        ``weights`` as in evaluate(), and so is the "weights" field."""
+        ``weights`` as in evaluate(), and so is the "weights" field.
+
+        ``manifold_k`` = a tuple of k (None: nothing below is launched or reported) adds the k-nearest-neighbour
+        manifold metrics on svae_op_pairwise_knn, which say how the sets differ: every step gains "manifold":
+        quality.manifold(X_t, R) = {"k", "precision", "recall", "density", "coverage", "nonfinite"}, R's pass
+        against itself done once; "real" gains "manifold_train", R against the first ``train_images`` training
+        images, the calibration line (what held-out real images score against the training set; None where
+        train_images <= max(k)); and the top level "manifold_k".  N - 1 < max(k) raises.  Their NaN counts enter
+        "nonfinite"; the tables join the one device -> host copy."""
         net, ds = self._net(weights), self.dataset
         if getattr(net.cfg, "external_generator_from", 0):
             raise ValueError("the PixelVAE head is not a trainer network")
@@ -550,6 +562,7 @@ class NoisyTrainer:
         if N < 2 * B:
             raise ValueError("sample_quality needs at least two whole windows of %d images, the %s split gives %d"
                              % (B, split, nwin))
+        mk = None if manifold_k is None else quality._ks(manifold_k, N, N)
         M = int(ds.train.shape[0])
         M = min(M, N) if train_images is None else int(train_images)
         if M < 1 or M > int(ds.train.shape[0]) or int(ds.train.shape[0]) < B:
@@ -578,7 +591,13 @@ class NoisyTrainer:
         _, nd, _ = quality.pairwise_stats(kept.view((T + 1) * N, D), [train], [], ksum=False)
         rms = (nd.view(T + 1, N) / D).sqrt()
         nnt = torch.stack([rms.mean(1), quality.median(rms), rms.min(1).values, torch.isnan(rms).sum(1).double()], 1)
-        host = torch.cat([torch.stack(tables).reshape(-1), nnt.reshape(-1)]).cpu().tolist()
+        flat = [torch.stack(tables).reshape(-1), nnt.reshape(-1)]
+        if mk is not None:
+            ry = quality.self_radii(R, mk)
+            flat += [quality.manifold_device(kept[t], R, mk, yy=ry) for t in range(T)]
+            if M > max(mk):
+                flat.append(quality.manifold_device(R, train, mk))
+        host = torch.cat(flat).cpu().tolist()
         nb = len(bwl)
         width = nb + 7
         nn_train = lambda i: dict(zip(("mean", "median", "min"), host[T * width + 4 * i:T * width + 4 * i + 3]))
@@ -591,9 +610,20 @@ class NoisyTrainer:
                           "nn_accuracy": {"samples": a["x"], "real": a["y"], "all": a["all"]},
                           "nn_real": r["nn_other"], "nn_train": nn_train(t)})
         bad += int(host[T * width + 4 * T + 3])
-        return self._tag({"split": split, "images": N, "seed": seed, "sigma0": bwl[nb // 2] ** 0.5,
-                          "bandwidth_scales": list(quality.SCALES), "train_images": M,
-                          "real": {"nn_train": nn_train(T)}, "steps": steps, "nonfinite": bad}, weights)
+        rep = {"split": split, "images": N, "seed": seed, "sigma0": bwl[nb // 2] ** 0.5,
+               "bandwidth_scales": list(quality.SCALES), "train_images": M,
+               "real": {"nn_train": nn_train(T)}, "steps": steps, "nonfinite": bad}
+        if mk is not None:
+            mw, at = 4 * len(mk) + 1, T * width + 4 * (T + 1)
+            for t in range(T):
+                steps[t]["manifold"] = quality.unpack_manifold(host[at + t * mw:at + (t + 1) * mw], mk)
+                rep["nonfinite"] += steps[t]["manifold"]["nonfinite"]
+            rep["real"]["manifold_train"] = None
+            if M > max(mk):
+                rep["real"]["manifold_train"] = quality.unpack_manifold(host[at + T * mw:at + (T + 1) * mw], mk)
+                rep["nonfinite"] += rep["real"]["manifold_train"]["nonfinite"]
+            rep["manifold_k"] = list(mk)
+        return self._tag(rep, weights)
 
     def write_sample_quality(self, **kw):
         """One line {"iteration", <sample_quality(**kw)>}: logged at info level and, with a base_dir, appended to

@@ -44,6 +44,9 @@ def parse(argv=None):
                     help="report NoisyTrainer.sample_quality() instead: per-step kernel MMD^2, 1-nearest-neighbour "
                          "two-sample accuracy and nearest-training-image distances of generated samples against the "
                          "split's whole windows; written to sample_quality.json")
+    ap.add_argument("--quality_k", default=None, metavar="K,K",
+                    help="with --sample_quality: also report k-nearest-neighbour precision, recall, density and "
+                         "coverage per step at these k, e.g. 3,5 (sample_quality's manifold_k; default: off)")
     ap.add_argument("--spectrum", action="store_true",
                     help="report NoisyTrainer.spectrum() of the same forwards instead: per step the radially averaged "
                          "power spectrum of the outputs and of their error against the clean images' own, band SNR, "
@@ -136,7 +139,14 @@ def main(argv=None):
         report, name = trainer.sample_quality, "sample_quality.json"
     if a.spectrum:
         report, name = trainer.spectrum, "spectrum.json"
-    row.update(report(split=a.split, num_batches=a.num_batches, seed=a.seed, weights="ema" if a.ema else "train"))
+    kw = {}
+    if a.quality_k:
+        if not a.sample_quality:
+            print("--quality_k goes with --sample_quality")
+            return 1
+        kw["manifold_k"] = [int(k) for k in a.quality_k.split(",")]
+    row.update(report(split=a.split, num_batches=a.num_batches, seed=a.seed, weights="ema" if a.ema else "train",
+                      **kw))
     line = json.dumps(row)
     with open(os.path.join(base_dir, name), "w") as f:
         f.write(line + "\n")

@@ -1,4 +1,4 @@
-"""VGPR / AGPR / spill / LDS / occupancy of the kernels of one csrc file (gfx950).
+"""VGPR / AGPR / spill / scratch / LDS / occupancy of the kernels of one csrc file (gfx950).
     python tools/resource_usage.py gemm_bf16.hip [name-filter]"""
 import os
 import re
@@ -27,6 +27,6 @@ for line in r.stderr.splitlines():
 flt = sys.argv[2] if len(sys.argv) > 2 else ""
 for d in out:
     if flt in d["name"]:
-        print("%-90s VGPR %4s AGPR %4s spill %3s/%3s occ %s LDS %s" % (
+        print("%-90s VGPR %4s AGPR %4s spill %3s/%3s scratch %s occ %s LDS %s" % (
             d["name"][:90], d.get("VGPRs"), d.get("AGPRs"), d.get("VGPRs Spill"), d.get("SGPRs Spill"),
-            d.get("Occupancy [waves/SIMD]"), d.get("LDS Size [bytes/block]")))
+            d.get("ScratchSize [bytes/lane]"), d.get("Occupancy [waves/SIMD]"), d.get("LDS Size [bytes/block]")))

@@ -48,6 +48,9 @@ def parse(argv=None):
                     help="append NoisyTrainer.sample_quality() against the test split (per-step kernel MMD^2, "
                          "1-nearest-neighbour two-sample accuracy and nearest-training-image distances of generated "
                          "samples) to <model dir>/sample_quality.jsonl every N iterations (0: off)")
+    ap.add_argument("--quality_k", default=None, metavar="K,K",
+                    help="with --quality_frequency: also report k-nearest-neighbour precision, recall, density and "
+                         "coverage per step at these k, e.g. 3,5 (sample_quality's manifold_k; default: off)")
     ap.add_argument("--spectrum_frequency", type=int, default=0,
                     help="append NoisyTrainer.spectrum() of the test split (per-step radially averaged power spectra "
                          "of the outputs, their error and the generated samples against the clean images' own) to "
@@ -140,7 +143,8 @@ def main(argv=None):
                  summary_freq=a.summary_freq, eval_frequency=a.eval_frequency,
                  info_frequency=a.info_frequency, quality_frequency=a.quality_frequency,
                  degradation=degradation(a), spectrum_frequency=a.spectrum_frequency, ema_decay=a.ema_decay,
-                 ema_warmup=not a.no_ema_warmup, ema_every=a.ema_every)
+                 ema_warmup=not a.no_ema_warmup, ema_every=a.ema_every,
+                 quality_k=[int(k) for k in a.quality_k.split(",")] if a.quality_k else None)
     if a.continue_training and os.path.exists(os.path.join(base_dir, "trainer.json")):
         trainer.load(base_dir)
         log.info("resumed at iteration %d" % trainer.iteration)
